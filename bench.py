@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the MI355X paged-attention hot path.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]          # the headline leg alone
+    python bench.py --gpus N --steps K --warmup W --full [--legs a,b] [--verify-gather] [--no-cpu-baseline]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
-        bench.py --gpus N --steps K --warmup W
+        bench.py --gpus N --steps K --warmup W [--full ...]
 
 Metric (BASELINE.json): "attn fwd TFLOPS (prefill) + KV GB/s (decode), Llama-3-8B GQA seq4k".
 The timed region is K steps of the PREFILL workload C2 (BASELINE configs[1]: Hq 32 / Hk 8 / D 128,
 one 4096-token sequence per GPU, bf16, paged KV with 16-token pages): `value` = attention-forward
-TFLOP/s, counted FA-style (4*q*kv*D*Hq/2 = 137.44 GFLOP per sequence), whole job over all GPUs.
-Three more workloads are timed the same way right after it and reported in the same JSON line:
+TFLOP/s, counted FA-style (4*q*kv*D*Hq/2 = 137.44 GFLOP per sequence), whole job over all GPUs; `ms_per_step` = wall clock
+of the K timed steps / K. A plain run does that and nothing else: set up, warm up, time the K steps, print the line.
+`--full` adds everything below: seven more workloads timed the same way right after it and reported in the same JSON
+line, the CPU baselines of C2 and C3 (one GPU, unless `--no-cpu-baseline`), `--legs` to pick workloads and `--verify-gather`:
   "decode"      C3 (configs[2]): batch 64 x kv_len 8192 per GPU, bf16 KV            -> KV GB/s
   "decode_fp8"  C5 (configs[4]): Hq 64 / Hk 8, batch 16 x kv_len 32768 per GPU, fp8-e4m3 KV -> KV GB/s
   "mixed"       C4 (configs[3]): the reference harness's mixed batch (32 decodes, 16 partial and 16 full prefills,
@@ -30,7 +33,9 @@ the only collectives are the timing barrier and the MAX over ranks of the measur
 `python bench.py --gpus N` with N > 1 and no torch.distributed environment starts the N ranks itself
 (torch.distributed.run as a child process, before this process touches a GPU) and fails loudly when the box has
 fewer than N GPUs.
-Inputs are synthetic (U(-1,1), seed 0 + rank), resident in HBM before the timed region starts.
+Inputs are synthetic (U(-1,1), seed 0 + rank), resident in HBM before the timed region starts, and the same from run to run.
+`--dump-outputs DIR`: after the timed steps rank 0 writes each timed workload's output tensor, as the last timed step left
+it, to DIR/<leg>.npy in float32 (see dump_output for the sample taken of the large ones; under 64 MB in all).
 """
 
 from __future__ import annotations
@@ -72,7 +77,12 @@ def spawn_ranks(args) -> int:
         port = s.getsockname()[1]
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}", "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.abspath(__file__), "--gpus", str(args.gpus), "--steps", str(args.steps), "--warmup", str(args.warmup)]
-    cmd += ["--legs", args.legs]
+    if args.full:
+        cmd.append("--full")
+    if args.legs:
+        cmd += ["--legs", args.legs]
+    if args.dump_outputs:
+        cmd += ["--dump-outputs", os.path.abspath(args.dump_outputs)]
     if args.no_cpu_baseline:
         cmd.append("--no-cpu-baseline")
     if args.verify_gather:
@@ -236,6 +246,28 @@ def timed_steps(call, steps, warmup, device, distributed):
     return wall, e0.elapsed_time(e1) * 1e-3 / steps
 
 
+# --dump-outputs: float32 bytes kept per leg. C2's output is 4096 x 32 x 128 = 64 MiB in float32, half of its rows are kept;
+# the other legs (--full) get 2 MiB each, so a whole --full run writes at most 32 + 7 * 2 = 46 MiB.
+DUMP_BYTES = {"prefill": 32 << 20}
+DUMP_BYTES_OTHER = 2 << 20
+
+
+def dump_output(directory, name, out):
+    """The leg's output tensor [tokens, Hq, D], as the last timed step left it, to <directory>/<name>.npy in float32.
+    A tensor above the leg's budget is cut to a fixed sample of its token rows (drawn without replacement by
+    numpy RandomState(0), in ascending order, all heads of a row): the same rows in every run of the same arguments."""
+    import numpy as np
+    import torch
+
+    rows = out.shape[0]
+    keep = max(1, DUMP_BYTES.get(name, DUMP_BYTES_OTHER) // (out[0].numel() * 4))
+    if keep < rows:
+        idx = np.sort(np.random.RandomState(0).choice(rows, keep, replace=False))
+        out = out[torch.from_numpy(idx).to(out.device)]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, name + ".npy"), out.float().cpu().numpy())
+
+
 def host_cpu_share():
     """CPUs this process may actually use: the cgroup CPU quota (a one-GPU job on the GPU box sees 256 CPUs and is given
     16), else the affinity mask, else the CPU count."""
@@ -349,13 +381,19 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=500)
     ap.add_argument("--warmup", type=int, default=50)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write each timed workload's output (rank 0's, as the last step left it) to DIR/<leg>.npy, float32")
+    ap.add_argument("--full", action="store_true",
+                    help="beyond the headline leg: the other seven workloads, the CPU baselines, --legs and --verify-gather")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: leave the CPU baselines out")
     ap.add_argument("--verify-gather", action="store_true",
-                    help="prefill_b8: assemble the ranks' outputs with one all_gather and compare with the unsharded batch (rank 0)")
-    ap.add_argument("--legs", default=",".join(ALL_LEGS),
-                    help="comma list of the workloads to run (profiles of ONE kernel: --legs prefill | decode | decode_fp8 | mixed | prefill_b8); "
-                         "the driver's default runs all of them, the headline value is the prefill leg's")
+                    help="--full, prefill_b8: assemble the ranks' outputs with one all_gather and compare with the unsharded batch (rank 0)")
+    ap.add_argument("--legs", default=None,
+                    help="--full: comma list of the workloads to run (profiles of ONE kernel: --legs prefill | decode | decode_fp8 | mixed | prefill_b8); "
+                         "--full alone runs all of them, the headline value is the prefill leg's")
     args = ap.parse_args()
+    if not args.full and (args.legs or args.verify_gather):
+        raise SystemExit("bench.py: --legs and --verify-gather belong to --full (a plain run times the headline prefill leg only)")
 
     global VERIFY_GATHER
     VERIFY_GATHER = args.verify_gather
@@ -391,7 +429,12 @@ def main():
         if distributed:
             dist.barrier()
 
-    legs = [x for x in args.legs.split(",") if x]
+    if not args.full:
+        legs = ["prefill"]
+    elif args.legs is None:
+        legs = list(ALL_LEGS)
+    else:
+        legs = [x for x in args.legs.split(",") if x]
     unknown = set(legs) - set(ALL_LEGS)
     if unknown or not legs:
         raise SystemExit(f"bench.py: --legs takes {', '.join(ALL_LEGS)}; got {args.legs!r}")
@@ -410,6 +453,8 @@ def main():
             dist.all_reduce(t, op=dist.ReduceOp.MAX)
         wall_max, launch_max = t.tolist()
         results[kind] = dict(w=w, kernel=kernel, wall=wall_max, per_launch=launch_max)
+        if args.dump_outputs and rank == 0:
+            dump_output(args.dump_outputs, kind, w["out"])
         if kind == "prefill_fp8":
             import ctypes
             results[kind]["workspace_bytes"] = int(_lib.load().mi355_attn_workspace_bytes(ctypes.byref(w["_keep"][0])))
@@ -499,7 +544,7 @@ def main():
                                    "config": {"workload": "C2's shape over an fp8-e4m3 cache: Hq32/Hk8/D128, 1 seq x 4096 tokens per GPU, causal, paged KV (16-token pages), "
                                                           "scales 1.0; the tiles are widened inside the kernel (reference :434-455), no 16-bit copy of the cache",
                                               "kernel": pf8["kernel"]}}
-        if n_gpus == 1 and not args.no_cpu_baseline:
+        if args.full and n_gpus == 1 and not args.no_cpu_baseline:
             if pf:
                 line["cpu_baseline"] = cpu_baseline(pf["w"], pf["w"]["out"])
             if dc:

@@ -87,7 +87,7 @@ def test_key_split_prefill_matches_the_oracle(case):
     torch.testing.assert_close(lse, ref_lse, atol=2e-2 if f8 is None else 3e-2, rtol=1e-3)
 
 
-def test_key_split_prefill_agrees_with_the_unsplit_kernel_at_chunk_size(monkeypatch):
+def test_key_split_prefill_agrees_with_the_unsplit_kernel_at_chunk_size(monkeypatch, tmp_path):
     """512-token chunk of one sequence against 8192 keys (Hq 32 / Hk 8 / D 128, bf16): forced split counts 1 .. 8 agree."""
     import subprocess
     import sys
@@ -116,7 +116,7 @@ print(_lib.last_kernel()); torch.save(out.cpu(), os.environ["MI355_OUT"])
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     outs = {}
     for splits in ("1", "2", "5", "8", ""):
-        env = dict(os.environ, MI355_ROOT=root, MI355_OUT=f"/tmp/ksplit_{splits or 'auto'}.pt", PYTHONDONTWRITEBYTECODE="1")
+        env = dict(os.environ, MI355_ROOT=root, MI355_OUT=str(tmp_path / f"ksplit_{splits or 'auto'}.pt"), PYTHONDONTWRITEBYTECODE="1")
         if splits:
             env["MI355_PREFILL_KEY_SPLITS"] = splits
         r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)

@@ -139,7 +139,7 @@ def test_bench_two_gpu_path_runs_or_refuses():
     import torch
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--legs", "mixed,prefill_b8,decode_b64", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--full", "--legs", "mixed,prefill_b8,decode_b64", "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--verify-gather"]
     env = dict(os.environ, MI355_BENCH_PREWARM_S="0.02", HSA_ENABLE_IPC_MODE_LEGACY="0")
     r = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600)
@@ -164,7 +164,7 @@ def test_bench_one_gpu_gather_check_and_new_legs():
     import sys
 
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--legs", "prefill_b8,decode_b64,prefill_512,prefill_fp8", "--steps", "3", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--legs", "prefill_b8,decode_b64,prefill_512,prefill_fp8", "--steps", "3", "--warmup", "1",
            "--no-cpu-baseline", "--verify-gather"]
     r = subprocess.run(cmd, capture_output=True, text=True, env=dict(os.environ, MI355_BENCH_PREWARM_S="0.02"), timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]

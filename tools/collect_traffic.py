@@ -19,7 +19,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def run_pass(counter, out, leg):
     subprocess.check_call(["rocprofv3", "--pmc", counter, "--kernel-trace", "--output-format", "csv", "-d", out, "--",
-                           "python3", os.path.join(ROOT, "bench.py"), "--no-cpu-baseline", "--steps", "5", "--warmup", "2", "--legs", leg],
+                           "python3", os.path.join(ROOT, "bench.py"), "--full", "--no-cpu-baseline", "--steps", "5", "--warmup", "2", "--legs", leg],
                           stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
     vals = {}
     for f in glob.glob(os.path.join(out, "*", "*counter_collection.csv")):
@@ -37,7 +37,7 @@ def main():
     os.makedirs(out_dir, exist_ok=True)
     sys.path.insert(0, ROOT)
     import bench
-    doc = {"csrc_sha256": bench.kernel_source_digest(), "command": "bench.py --no-cpu-baseline --steps 5 --warmup 2 --legs <leg>", "legs": {}}
+    doc = {"csrc_sha256": bench.kernel_source_digest(), "command": "bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --legs <leg>", "legs": {}}
     for leg in (sys.argv[2].split(",") if len(sys.argv) > 2 else ["prefill", "decode", "decode_fp8"]):
         fetch = run_pass("FETCH_SIZE", os.path.join(out_dir, f"pmc_fetch_{leg}"), leg)
         write = run_pass("WRITE_SIZE", os.path.join(out_dir, f"pmc_write_{leg}"), leg)
