@@ -26,9 +26,13 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 601 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 602 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.6.2  No change to the structs or the entry points. write_new_kv over an fp8 cache is accepted for steps with prefill
+ *          rows where the short-prompt kernel serves them (below 2048 keys; "prefill_mfma_lat_fp8"):
+ *          mi355_decode_write_fusable() answers 1 for such steps where it answered 0. It also answers 0 now for the 16-bit
+ *          steps of several sequences that the long-prefill kernel takes from 1024 / 1536 keys on, which the call refused.
  *   0.6.1  No change to the structs or the entry points. A prefill over an fp8 flash-layout cache (plain attention, head size
  *          128, >= 2048 keys) is read as fp8 by the fast prefill kernel itself ("prefill_mfma_pw_fp8"): such a call no
  *          longer asks for a 16-bit scratch cache - mi355_attn_workspace_bytes() answers the 256 KiB counter block, or
@@ -195,7 +199,10 @@ typedef struct mi355_attn_params {
    * key / value of EVERY query token (token t of sequence i = position seqused_k[i] - query_len_i + t); the launches attend
    * over them straight from these tensors and store them into their pages - by slot_mapping when one is handed in
    * (negative: not stored), else by position through the block table. One-token rows of such a step ride the decode launch
-   * and its fused write. */
+   * and its fused write.
+   * Library version >= 0.6.2: the same over an fp8 cache (e4m3 / e5m2) where the short-prompt kernel serves the prefill rows.
+   * The bytes stored are those of mi355_reshape_and_cache_flash (saturating fp8(x / scale)), and the step's own keys / values
+   * are attended over as a later step will read them from the cache: rounded through fp8(x / scale), not as the 16-bit rows. */
   int32_t write_new_kv;
   /* 0 (every op of the reference's backend path): causal - query t of a sequence sees keys j <= t + seqused_k - query_len.
    * 1: every query row sees ALL seqused_k keys of its sequence (prefill_flash_attention(causal=False),

@@ -115,9 +115,14 @@ __device__ __forceinline__ void lat_glds16(uint32_t voff, uint64_t sbase, uint32
 // a 4 KiB staging area of the wave behind the stages; when it has landed (the wait the loop has anyway) the same wave widens
 // it (v_cvt_scalef32_pk_*: exact) into the rows the 16-bit LDS-DMA would have filled, swizzle included, in front of the
 // tile's barrier. k_scale rides in Q', v_scale in 1 / l.
+// WR && KV8 (library 0.6.2): the fused write over an fp8 cache. The Q block that owns a token stores sat_fp8(x / scale) of its
+// rows (quantise_fp8x16, common.h: the bytes reshape_and_cache_flash stores). A 16-key group of this call's own tokens takes
+// the 16-bit stream from the linear tensors into its stage rows, and where a cache group is widened the same wave rounds
+// those sixteen rows through fp8 IN PLACE (round_staged_new): what reaches the matrix operands is T(fp8(x / scale)), the
+// value a later step reads from the cache - never the raw 16-bit row. Groups below ctx_len keep the fp8 staging path; the one
+// group that straddles ctx_len fetches both kinds per lane. A pure prefill (ctx_len 0) never touches the staging area.
 template <typename T, int NKQ, bool WR = false, int KV8 = 0>
 __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kernel(const LatArgs a) {
-  static_assert(!(WR && KV8), "the fused cache write is built for 16-bit caches");
   constexpr int EB = KV8 ? 1 : 2;                   // bytes per cache element
   using KVT = std::conditional_t<KV8 == 2, e5m2_t, std::conditional_t<KV8 == 1, e4m3_t, T>>;
   constexpr int D = 128, ROWB = D * 2;              // 256-byte rows of 16 chunks of 16 bytes
@@ -197,7 +202,25 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
   const int new_st = (int)p.new_stride_token;
   const char* const knew = (const char*)p.k_new + (int64_t)head * p.new_stride_head * 2;
   const char* const vnew = (const char*)p.v_new + (int64_t)head * p.new_stride_head * 2;
-  if constexpr (fused) {
+  // (fp8 cache: the divisors of the quantising store, as reshape_and_cache_flash takes them)
+  const float k_div = (fused && KV8 && p.k_scale) ? p.k_scale[0] : 1.0f, v_div = (fused && KV8 && p.v_scale) ? p.v_scale[0] : 1.0f;
+  if constexpr (fused && KV8) {
+    // a row of 128 elements is 128 bytes per matrix: eight lanes of 16 bytes each, one store per matrix and row, 8 NW rows a pass
+    const int tok_end = min(tok0 + BQ, q_len);
+    for (int tok = tok0 + (tid >> 3); tok < tok_end; tok += NW * 8) {
+      int64_t slot;
+      if (p.slot_mapping) slot = p.slot_mapping[q_start + tok];
+      else if (p.slot_mapping_i32) slot = p.slot_mapping_i32[q_start + tok];
+      else { const int pos = ctx_len + tok; slot = (int64_t)bt[pos >> a.page_shift] * p.page_size + (pos & page_mask); }
+      if (slot < 0) continue;
+      const int64_t pg = slot >> a.page_shift, sl = slot & page_mask;
+      const int64_t src = (int64_t)(q_start + tok) * (new_st * 2) + (tid & 7) * 32;
+      const lu32x4_t k0 = *(const lu32x4_t*)(knew + src), k1 = *(const lu32x4_t*)(knew + src + 16);
+      const lu32x4_t v0 = *(const lu32x4_t*)(vnew + src), v1 = *(const lu32x4_t*)(vnew + src + 16);
+      *(lu32x4_t*)((char*)kbase + pg * (int64_t)a.k_page_stride + sl * (int64_t)a.k_slot_stride + (tid & 7) * 16) = quantise_fp8x16<T, KVT>(k0, k1, k_div);
+      *(lu32x4_t*)((char*)vbase + pg * (int64_t)a.v_page_stride + sl * (int64_t)a.v_slot_stride + (tid & 7) * 16) = quantise_fp8x16<T, KVT>(v0, v1, v_div);
+    }
+  } else if constexpr (fused) {
     const int tok_end = min(tok0 + BQ, q_len);
     for (int tok = tok0 + (tid >> 4); tok < tok_end; tok += NW * 4) {
       int64_t slot;
@@ -247,14 +270,16 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
     const uint64_t kb = (uint64_t)kbase + k_off, vb = (uint64_t)vbase + v_off;
     const uint32_t dst = smem_base + stage_off + (uint32_t)wave * (16 * ROWB);
     if constexpr (KV8) {       // two pieces per matrix into the staging area; rows past the sequence fetch its last row
-      const int maxr = max(seq_len - 1 - key0, 0);
+      if (!fused || key0 + 16 <= ctx_len) {      // (fused: compile time; a group with a new row in it takes the 16-bit stream below)
+        const int maxr = max(seq_len - 1 - key0, 0);
 #pragma unroll
-      for (int j = 0; j < 2; ++j) {
-        const int r = min(8 * j + r8, maxr);
-        lat_glds16((uint32_t)(r * (int)a.k_slot_stride + (c8 << 4)), kb, stg_lds + j * 1024);
-        lat_glds16((uint32_t)(r * (int)a.v_slot_stride + (c8 << 4)), vb, stg_lds + 2048 + j * 1024);
+        for (int j = 0; j < 2; ++j) {
+          const int r = min(8 * j + r8, maxr);
+          lat_glds16((uint32_t)(r * (int)a.k_slot_stride + (c8 << 4)), kb, stg_lds + j * 1024);
+          lat_glds16((uint32_t)(r * (int)a.v_slot_stride + (c8 << 4)), vb, stg_lds + 2048 + j * 1024);
+        }
+        return;
       }
-      return;
     }
     if (fused && key0 + 16 > ctx_len) {        // (fused: compile time)
       // FUSED CACHE WRITE (write_new_kv): keys at positions >= ctx_len are this call's own tokens and come from the linear
@@ -270,6 +295,23 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
           const int rig = 4 * j + rin, r = min(rig, max(seq_len - 1 - key0, 0));        // (rows past the sequence: its last row)
           lat_glds16((uint32_t)(r * new_st * 2 + ((ch ^ rig) << 4)), knb, dst + j * 1024);
           lat_glds16((uint32_t)(r * new_st * 2 + ((ch ^ (2 * (rig & 7))) << 4)), vnb, dst + KBUF + j * 1024);
+        }
+      } else if constexpr (KV8) {
+        // the straddling group over an fp8 cache: its cache rows (positions < ctx_len; the piece's other lanes re-fetch the last
+        // of them) as fp8 into the staging area, its new rows (the other lanes: the first / last of them) as 16-bit into the
+        // stage - widen_staged takes each row from where its kind landed
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int64_t r = min(key0 + 8 * j + r8, ctx_len - 1) - key0;
+          glds16((const char*)kb + r * (int)a.k_slot_stride + (c8 << 4), stg_lds + j * 1024);
+          glds16((const char*)vb + r * (int)a.v_slot_stride + (c8 << 4), stg_lds + 2048 + j * 1024);
+        }
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const int rig = 4 * j + rin;
+          const int64_t row = (int64_t)(q_start + min(max(key0 + rig, ctx_len), seq_len - 1) - ctx_len) * (new_st * 2);
+          glds16(knew + row + ((ch ^ rig) << 4), dst + j * 1024);
+          glds16(vnew + row + ((ch ^ (2 * (rig & 7))) << 4), dst + KBUF + j * 1024);
         }
       } else {
 #pragma unroll
@@ -299,10 +341,34 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
     }
   };
   // fp8: this wave's staged group (landed: the caller waited) widened into its sixteen rows of stage `stage_off`
-  auto widen_staged = [&](uint32_t stage_off) {
+  // fused write over an fp8 cache: this wave's group of tile `tile` holds rows of this call's own tokens, fetched as 16-bit
+  // (landed): every 16-byte chunk of its sixteen rows through fp8 and back where it lies - sat_fp8(x / scale) by the store's
+  // own conversion, widened unscaled - so no swizzle arithmetic; a lane takes chunks lane + 64 i (row 4 i + lane / 16), two a call
+  auto round_staged_new = [&](char* kd) {
+#pragma unroll
+    for (int m = 0; m < 2; ++m)              // K, V
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        char* const c0 = kd + m * KBUF + h * 2048 + lane * 16;
+        const lu32x4_t q8 = quantise_fp8x16<T, KVT>(*(const lu32x4_t*)c0, *(const lu32x4_t*)(c0 + 1024), m ? v_div : k_div);
+        uint32_t o[8];
+#pragma unroll
+        for (int w = 0; w < 4; ++w) widen_fp8x4<T, KVT>(q8[w], o[2 * w], o[2 * w + 1]);
+        *(lu32x4_t*)c0 = lu32x4_t{o[0], o[1], o[2], o[3]};
+        *(lu32x4_t*)(c0 + 1024) = lu32x4_t{o[4], o[5], o[6], o[7]};
+      }
+  };
+  auto widen_staged = [&](int tile, uint32_t stage_off) {
     if constexpr (KV8) {
       char* const kd = smem + stage_off + wave * (16 * ROWB);
       char* const vd = kd + KBUF;
+      int n_cache = 16;                      // rows of the group that came from the cache (fused: wave-uniform per tile)
+      if constexpr (fused) {
+        const int key0 = min(tile * NW + wave, last_group) << 4;
+        n_cache = ctx_len - key0;
+        if (n_cache < 16) round_staged_new(kd);      // (the straddling group: all sixteen rows; its cache rows are overwritten below)
+        if (n_cache <= 0) return;
+      }
 #pragma unroll
       for (int m = 0; m < 2; ++m)            // K, V
 #pragma unroll
@@ -313,6 +379,7 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
           for (int w = 0; w < 4; ++w) widen_fp8x4<T, KVT>(in[w], o[2 * w], o[2 * w + 1]);
           const int rig = 8 * j + r8, f = m ? 2 * (rig & 7) : rig;
           char* const row = (m ? vd : kd) + rig * ROWB;
+          if (fused && rig >= n_cache) continue;        // (fused: compile time) a new row of the straddling group: rounded above
           *(lu32x4_t*)(row + (((2 * c8) ^ f) << 4)) = lu32x4_t{o[0], o[1], o[2], o[3]};
           *(lu32x4_t*)(row + (((2 * c8 + 1) ^ f) << 4)) = lu32x4_t{o[4], o[5], o[6], o[7]};
         }
@@ -322,6 +389,10 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
   for (int t = 0; t < PD; ++t)
     if (t < tile_hi) issue_dma(t, t * STAGE);
   // wait until this wave's pieces of the NEXT tile have landed: `newer` tiles behind it may stay in flight
+  // (a wave's consecutive tiles may be of different kinds - 4 instructions of an fp8 group, IPT of a 16-bit one: the counted
+  // waits below hold for equal kinds only, so anything but PD = 1, where every wait is for everything, has to count what the
+  // wave issued)
+  static_assert(!(WR && KV8) || PD == 1, "mixed tile kinds: the counted waits assume IPT instructions per tile");
   auto wait_next_tile = [&](int newer) {
     if (PD >= 3 && newer >= 2) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(2 * IPT) : "memory");
     else if (PD >= 2 && newer == 1) asm volatile("s_waitcnt vmcnt(%0)" :: "n"(IPT) : "memory");
@@ -378,7 +449,7 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
     for (int c = 0; c < KSTEPS; ++c) asm volatile("" : "+v"(qf[cg][c]));
   LAT_WG_STAMP(wg_tb);   // Q landed, first tiles requested
   wait_next_tile(max(0, min(PD - 1, tile_hi - 1)));      // the first tile has landed
-  if (tile_hi > 0) widen_staged(0);
+  if (tile_hi > 0) widen_staged(0, 0);
   __syncthreads();
   LAT_WG_STAMP(wg_t1);
 
@@ -479,7 +550,7 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
         if (t + PD < tile_hi) issue_dma(t + PD, ((u + PD) % NST) * STAGE);
         if (t * TILE + kh * 32 < wave_keys) compute_tile(t, cur);
         wait_next_tile(max(0, min(t + PD, tile_hi - 1) - (t + 1)));     // this wave's pieces of tile t+1 have landed ...
-        if (t + 1 < tile_hi) widen_staged(((u + 1) % NST) * STAGE);     // (fp8: ... in its staging area; widened into tile t+1's stage, which tile t-1 left at the last barrier)
+        if (t + 1 < tile_hi) widen_staged(t + 1, ((u + 1) % NST) * STAGE);     // (fp8: ... in its staging area; widened into tile t+1's stage, which tile t-1 left at the last barrier)
         __syncthreads();                                 // ... and so have everyone else's; stage `cur` is free
       }
     }
@@ -573,16 +644,20 @@ bool prefill_lat_selected(const mi355_attn_params& p) {
 // LDS-DMA kernels (prefill_mfma.hip) - they attend over the step's new keys straight from the linear tensors and the Q block
 // that owns a token stores its rows - and, in a step that may carry one-token rows as well (several sequences of unequal
 // query lengths: two launches, api.hip), those rows on the split-KV decode kernel's own fused write. Not the long-prefill
-// kernel (prefill_pw_kernel: from 2048 keys on, 1536 / 1024 with several sequences), key-split launches, features, fp8 caches.
+// kernel (prefill_pw_kernel: from 2048 keys on, 1536 / 1024 with several sequences), key-split launches, features.
+// An fp8 cache (library 0.6.2): exactly where THIS kernel is the one selected - its WR && KV8 instantiations; the LDS-DMA
+// kernels do not read fp8. The answer is launch_prefill's: what it refuses (prefill_pw_kernel's steps) is refused here.
 bool prefill_write_fusable(const mi355_attn_params& p) {
   mi355_attn_params q = p;
   q.write_new_kv = 1;
   if (!q.k_new || !q.v_new || q.max_seqlen_q <= 1 || q.non_causal || q.skip_decodes || q.only_decodes || q.new_kv_all_rows) return false;
   if (q.kernel_select != MI355_SELECT_AUTO) return false;
   if (q.softcap > 0.0f || q.alibi_slopes || q.sliding_window > 0) return false;
-  if (q.kv_dtype != q.q_dtype || q.new_stride_token % 8 != 0 || q.new_stride_head % 8 != 0 || ((uintptr_t)q.k_new & 15) != 0 || ((uintptr_t)q.v_new & 15) != 0) return false;
+  const bool fp8 = q.kv_dtype == MI355_FP8_E4M3 || q.kv_dtype == MI355_FP8_E5M2;
+  if ((q.kv_dtype != q.q_dtype && !fp8) || q.new_stride_token % 8 != 0 || q.new_stride_head % 8 != 0 || ((uintptr_t)q.k_new & 15) != 0 || ((uintptr_t)q.v_new & 15) != 0) return false;
   if (q.new_stride_token <= 0 || q.new_stride_token >= (1 << 22)) return false;
-  if (!prefill_runs_without_key_splits(q) || !(prefill_lat_selected(q) || prefill_dma_selected(q))) return false;     // (a key-split launch writes partial outputs: no fused write)
+  if (!prefill_runs_without_key_splits(q) || prefill_pw_selected(q, nullptr)) return false;     // (a key-split launch writes partial outputs: no fused write)
+  if (!(prefill_lat_selected(q) || (!fp8 && prefill_dma_selected(q)))) return false;
   const bool single_launch = q.num_seqs == 1 || (int64_t)q.num_seqs * q.max_seqlen_q == q.num_tokens;
   if (single_launch) return true;
   mi355_attn_params d = q;            // the one-token rows' launch
@@ -594,8 +669,8 @@ bool prefill_lat_applicable(const mi355_attn_params& p) {
   if (!prefill_supported(p)) return false;
   const bool feat = p.softcap > 0.0f || p.alibi_slopes != nullptr || p.sliding_window > 0;
   const int G = p.num_q_heads / p.num_kv_heads;
-  const bool fp8 = p.kv_dtype == MI355_FP8_E4M3 || p.kv_dtype == MI355_FP8_E5M2;      // (round 4: its KV8 instantiations; no fused cache write there)
-  return !feat && p.head_size == 128 && (p.kv_dtype == p.q_dtype || (fp8 && !p.write_new_kv)) && G <= kLatRows && ((uintptr_t)p.out & 7) == 0;
+  const bool fp8 = p.kv_dtype == MI355_FP8_E4M3 || p.kv_dtype == MI355_FP8_E5M2;      // (round 4: its KV8 instantiations; 0.6.2: WR && KV8)
+  return !feat && p.head_size == 128 && (p.kv_dtype == p.q_dtype || fp8) && G <= kLatRows && ((uintptr_t)p.out & 7) == 0;
 }
 
 template <typename T, int NKQ, bool WR, int KV8 = 0>
@@ -631,6 +706,14 @@ int launch_prefill_lat(const mi355_attn_params& p, hipStream_t stream) {
   const long wgs = ((long)p.num_tokens / (kLatRows / (p.num_q_heads / p.num_kv_heads)) + p.num_seqs) * p.num_kv_heads;
   const bool eight = pin ? pin == 8 : wgs <= 288;
   const bool bf = p.q_dtype == MI355_BF16;
+  if (p.write_new_kv && p.kv_dtype == MI355_FP8_E4M3) {
+    if (eight) return bf ? launch_lat_t<bf16_t, 4, true, 1>(p, stream) : launch_lat_t<f16_t, 4, true, 1>(p, stream);
+    return bf ? launch_lat_t<bf16_t, 2, true, 1>(p, stream) : launch_lat_t<f16_t, 2, true, 1>(p, stream);
+  }
+  if (p.write_new_kv && p.kv_dtype == MI355_FP8_E5M2) {
+    if (eight) return bf ? launch_lat_t<bf16_t, 4, true, 2>(p, stream) : launch_lat_t<f16_t, 4, true, 2>(p, stream);
+    return bf ? launch_lat_t<bf16_t, 2, true, 2>(p, stream) : launch_lat_t<f16_t, 2, true, 2>(p, stream);
+  }
   if (p.kv_dtype == MI355_FP8_E4M3) {
     if (eight) return bf ? launch_lat_t<bf16_t, 4, false, 1>(p, stream) : launch_lat_t<f16_t, 4, false, 1>(p, stream);
     return bf ? launch_lat_t<bf16_t, 2, false, 1>(p, stream) : launch_lat_t<f16_t, 2, false, 1>(p, stream);

@@ -30,6 +30,9 @@ import os  # noqa: E402
 logger = init_logger(__name__)
 _FUSED_DECODE_WRITE = os.environ.get("MI355_FUSED_DECODE_WRITE", "1") != "0"   # A/B switch: 0 = always two launches
 _FUSED_PREFILL_WRITE = os.environ.get("MI355_FUSED_PREFILL_WRITE", "1") != "0"   # A/B switch: 0 = cache write and attention as two calls for prefill steps too
+# the same over an fp8 cache (library 0.6.2): OFF by default - measured slower than the pair of calls (23.1 against 17.3 us per layer
+# at 1 x 512, profiles/r05/fused_prefill_write_fp8.log); =1 takes the fused path where the library answers for the step
+_FUSED_PREFILL_WRITE_FP8 = os.environ.get("MI355_FUSED_PREFILL_WRITE_FP8", "0") == "1"
 _lib.load()  # fail at import, not at the first forward, if the HIP library is missing
 
 
@@ -310,8 +313,12 @@ class MI355AttentionImpl(AttentionImpl):
         # A plain step that is not a decode step (round 4): the op issues ONE launch where the short-prompt kernel serves the
         # step with the cache write inside (library 0.6.0: a prompt of a few hundred tokens - the reference's own latency
         # protocol), and the pair of calls below otherwise - same cache bytes, same output. MI355_FUSED_PREFILL_WRITE=0 keeps the pair.
-        if (plain and attn_metadata.max_query_len > 1 and self.kv_sharing_target_layer_name is None and not self.kv_cache_dtype.startswith("fp8")
+        # An fp8 cache (library 0.6.2) takes the same branch only with MI355_FUSED_PREFILL_WRITE_FP8=1 (see above).
+        fp8 = self.kv_cache_dtype.startswith("fp8")
+        if (plain and attn_metadata.max_query_len > 1 and self.kv_sharing_target_layer_name is None and (not fp8 or _FUSED_PREFILL_WRITE_FP8)
                 and not (self.use_irope and attn_metadata.local_attn_metadata is not None) and _FUSED_PREFILL_WRITE):
+            if fp8:
+                self._check_q_scale(layer)
             q = query[:num_actual_tokens]
             out = output[:num_actual_tokens]
             if out.dim() == 2:

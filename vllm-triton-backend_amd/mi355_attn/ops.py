@@ -86,9 +86,12 @@ def _prefill_attention_and_cache_write_impl(q, key, value, key_cache, value_cach
     """A plain prefill (or mixed) step: ONE launch when the short-prompt kernel serves it with the cache write inside, else the
     cache write followed by the attention: the same cache bytes and the same output either way."""
     n = q.shape[0]
-    if kv_cache_dtype not in _FP8 and _prefill_attention_and_cache_write(
-            q, key, value, key_cache, value_cache, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, softmax_scale, block_table,
-            slot_mapping if slot_mapping.shape[0] >= n else None):
+    kc, vc = key_cache, value_cache
+    if kv_cache_dtype in _FP8 and kc.dtype == torch.uint8:
+        kc, vc = kc.view(_FP8[kv_cache_dtype]), vc.view(_FP8[kv_cache_dtype])
+    if _prefill_attention_and_cache_write(
+            q, key, value, kc, vc, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, softmax_scale, block_table,
+            slot_mapping if slot_mapping.shape[0] >= n else None, *((k_scale, v_scale) if kv_cache_dtype in _FP8 else ())):
         return
     _reshape_and_cache_flash(key, value, key_cache, value_cache, slot_mapping, kv_cache_dtype, k_scale, v_scale)
     _unified_attention_impl(q, key_cache, value_cache, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, softmax_scale, -1, -1, block_table, 0.0,
