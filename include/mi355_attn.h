@@ -26,9 +26,14 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 602 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 700 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.7.0  Attention sinks. mi355_attn_params grew at its END (sinks): zero the struct before filling it and nothing changes -
+ *          a call with sinks == NULL computes what 0.6.2 computed, bit for bit, on the same kernel with the same workspace.
+ *          With sinks every kernel family adds the row's sink to its softmax denominator and to lse (see the field); dispatch,
+ *          mi355_last_kernel() and mi355_attn_workspace_bytes() do not depend on it. Refused with sinks (MI355_ERR_UNSUPPORTED):
+ *          non_causal, write_new_kv (mi355_decode_write_fusable() answers 0) and the two legacy entry points.
  *   0.6.2  No change to the structs or the entry points. write_new_kv over an fp8 cache is accepted for steps with prefill
  *          rows where the short-prompt kernel serves them (below 2048 keys; "prefill_mfma_lat_fp8"):
  *          mi355_decode_write_fusable() answers 1 for such steps where it answered 0. It also answers 0 now for the 16-bit
@@ -229,6 +234,18 @@ typedef struct mi355_attn_params {
    * tokens (speculative decoding with k drafts: 1 + k) says so here and gets N = that, up to 32 / G (two column groups;
    * ignored where they do not apply: features, head size 256, more). Host-known, so capture-stable. */
   int32_t decode_rows_hint;
+
+  /* library version >= 0.7.0 (not in the reference's unified_attention; vLLM hands `sinks` to the attention implementation,
+   * the gpt-oss models carry one per layer). Attention sinks: one learned logit per query head, fp32 [Hq], in the natural-log
+   * domain of the SCALED scores - neither the softmax scale nor the soft-cap nor an ALiBi bias is applied to it, and neither
+   * the causal mask nor the sliding window masks it. It joins the row's softmax denominator and carries no value: with x_j
+   * the row's visible scores after scale, cap and bias,
+   *     out = sum_j exp(x_j) v_j / (exp(sinks[h]) + sum_j exp(x_j)),   lse = log(exp(sinks[h]) + sum_j exp(x_j)).
+   * A row that sees no key gets out 0 and lse = sinks[h]. lse INCLUDES the sink, so partial results over disjoint key ranges
+   * still merge exactly by the formula at `lse` (mi355_merge_attention_partials, the cross-GPU split-KV exchange) PROVIDED
+   * EXACTLY ONE of the partial calls carried the sinks and the others passed NULL. NULL = no sinks. Not with non_causal, not
+   * with write_new_kv, not through the legacy entry points. */
+  const float* sinks;
 } mi355_attn_params;
 
 /*
@@ -326,6 +343,7 @@ MI355_API int mi355_unified_attention(const mi355_attn_params* p, void* workspac
  *   mi355_paged_attention_v0 - `paged_attention_triton_2d/3d` (legacy/triton_paged_decode_attention_2d.py:283-398,
  *     ..._3d.py:348-499): one query token per sequence (max_seqlen_q == 1, num_tokens == num_seqs), every key from the
  *     cache (k_new / v_new must be NULL).
+ * Neither op has attention sinks: a block with sinks != NULL is refused (MI355_ERR_UNSUPPORTED).
  * mi355_attn_workspace_bytes() answers for these calls when the block is filled the same way (skip_decodes = 1 for the
  * first).
  */
@@ -347,6 +365,8 @@ MI355_API int mi355_decode_write_fusable(const mi355_attn_params* p);
  * part_out [parts, num_tokens, Hq, D] contiguous, in the query type `dtype` (bf16 / f16: what the kernels wrote, no f32
  * copy); part_lse [parts, num_tokens, Hq] f32 (a range that saw no key: -inf). out [num_tokens, Hq, D] with the given
  * element strides, lse [num_tokens, Hq] or NULL. 1 <= parts <= 8. One launch, no workspace.
+ * Attention sinks (0.7.0): the partial lse's include the sink of the call that carried it, so the merge needs no sinks
+ * argument - exactly one of the partial calls is made with sinks, the others without.
  */
 MI355_API int mi355_merge_attention_partials(const void* part_out, const float* part_lse, int parts, void* out, float* lse, int dtype,
                                              int num_tokens, int num_q_heads, int head_size, int64_t out_stride_token, int64_t out_stride_head,

@@ -60,6 +60,12 @@ static int validate(const mi355_attn_params* p) {
     set_error("non_causal attention takes neither a sliding window nor ALiBi slopes nor a fused cache write");
     return MI355_ERR_UNSUPPORTED;
   }
+  // attention sinks (library 0.7.0): a per-row epilogue of the causal kernels. Not with non_causal (the reference's op of that
+  // name has none), not with a fused cache write (out of scope: the caller issues mi355_reshape_and_cache_flash first).
+  if (p->sinks && (p->non_causal || p->write_new_kv)) {
+    set_error("sinks go with neither non_causal attention nor a fused cache write (write_new_kv)");
+    return MI355_ERR_UNSUPPORTED;
+  }
   if (p->slot_mapping && p->slot_mapping_i32) { set_error("at most one of slot_mapping / slot_mapping_i32 may be non-NULL"); return MI355_ERR_BAD_ARG; }
   if (p->new_kv_all_rows && (!p->k_new || p->write_new_kv)) { set_error("new_kv_all_rows needs k_new / v_new and excludes write_new_kv"); return MI355_ERR_BAD_ARG; }
   if (p->write_new_kv) {
@@ -236,6 +242,7 @@ int mi355_unified_attention(const mi355_attn_params* p, void* workspace, size_t 
 
 int mi355_decode_write_fusable(const mi355_attn_params* p) {
   if (!p || p->num_tokens <= 0 || p->num_seqs <= 0) return 0;
+  if (p->sinks) return 0;                        // (validate() refuses the pair)
   if (p->max_seqlen_q == 1 && p->num_tokens == p->num_seqs) return decode_write_fusable(*p) ? 1 : 0;
   return prefill_write_fusable(*p) ? 1 : 0;      // (library 0.6.0: a prefill step in one launch of the short-prompt kernel)
 }
@@ -244,6 +251,7 @@ int mi355_context_attention_fwd_v0(const mi355_attn_params* p, void* workspace, 
   if (!p) { set_error("params is NULL"); return MI355_ERR_BAD_ARG; }
   if (!p->k_new || !p->v_new) { set_error("context_attention_fwd needs the linear k_new / v_new of the tokens being prefilled"); return MI355_ERR_BAD_ARG; }
   if (p->only_decodes) { set_error("context_attention_fwd never computes query_len == 1 rows (only_decodes must be 0)"); return MI355_ERR_BAD_ARG; }
+  if (p->sinks) { set_error("context_attention_fwd has no attention sinks (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
   mi355_attn_params q = *p;
   q.skip_decodes = 1;                          // rows of query_len == 1 sequences stay untouched (triton_prefix_prefill.py:83-84)
   return mi355_unified_attention(&q, workspace, workspace_bytes, stream);
@@ -252,6 +260,7 @@ int mi355_context_attention_fwd_v0(const mi355_attn_params* p, void* workspace, 
 int mi355_paged_attention_v0(const mi355_attn_params* p, void* workspace, size_t workspace_bytes, mi355_stream_t stream) {
   if (!p) { set_error("params is NULL"); return MI355_ERR_BAD_ARG; }
   if (p->k_new || p->v_new) { set_error("paged_attention reads every key from the cache (k_new / v_new must be NULL)"); return MI355_ERR_BAD_ARG; }
+  if (p->sinks) { set_error("paged_attention has no attention sinks (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
   if (p->max_seqlen_q != 1 || p->num_tokens != p->num_seqs) {
     set_error("paged_attention is a decode op: one query token per sequence (max_seqlen_q %d, num_tokens %d, num_seqs %d)", p->max_seqlen_q, p->num_tokens, p->num_seqs);
     return MI355_ERR_BAD_ARG;

@@ -419,6 +419,27 @@ __device__ __forceinline__ float softcap_fast(float s, float cap, float k) {
   return cap - 2.0f * cap * __builtin_amdgcn_rcpf(1.0f + e);
 }
 
+// Attention sink (mi355_attn_params::sinks, library 0.7.0): one more term exp(sink) in a row's softmax denominator, with no
+// value behind it. Every kernel family ends a row with a pair (m, l) - the sum l of its weights relative to a reference m
+// (the running maximum, or whatever fixed reference the kernel's tiles used) - and the sink enters THERE, once, where the
+// pair is final: never in a partial that a merge folds later. Max form, m' = max(m, s), l' = l e^(m - m') + e^(s - m')
+// (l + e^(s - m) overflows for a row whose every score lies far below its sink). Returns e^(m - m'), the factor the row's
+// un-normalised output takes beside 1 / l'. A row without a visible key (l == 0, m anything) becomes (s, 1): out 0, lse = s;
+// a sink of -inf leaves (m, l) as they are. LOG2: m is in the log2 domain (the matrix-core kernels); `sink` is natural-log.
+template <bool LOG2>
+__device__ __forceinline__ float fold_sink(float& m, float& l, float sink) {
+  const float s = LOG2 ? sink * 1.4426950408889634f : sink;
+  if (!(l > 0.0f)) {
+    if (s > -INFINITY) { m = s; l = 1.0f; }
+    return 0.0f;
+  }
+  const float mn = fmaxf(m, s);
+  const float w = LOG2 ? __builtin_amdgcn_exp2f(m - mn) : expf(m - mn);
+  l = l * w + (LOG2 ? __builtin_amdgcn_exp2f(s - mn) : expf(s - mn));
+  m = mn;
+  return w;
+}
+
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------

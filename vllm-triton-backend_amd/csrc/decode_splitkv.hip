@@ -350,7 +350,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
 #pragma unroll
       for (int b = 0; b < DBLK; ++b)
         if (!PAD || 16 * b + 4 * grp < a.d_valid) *(u32x2_t*)((uint16_t*)p.out + o + 16 * b + 4 * grp) = u32x2_t{0, 0};
-      if (p.lse && grp == 0) p.lse[(int64_t)token[cg] * p.lse_stride_token + hq[cg]] = -INFINITY;
+      if (p.lse && grp == 0) p.lse[(int64_t)token[cg] * p.lse_stride_token + hq[cg]] = p.sinks ? p.sinks[hq[cg]] : -INFINITY;   // (the sink alone)
     }
     return;
   }
@@ -704,10 +704,11 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
       for (int i = 0; i < 4; ++i)
         if (i < nw) om[j] += *(const f32x4_t*)((const float*)(smem + i * LDS_PER_WAVE) + ((wave_in_wg + 4 * j) * 64 + lane) * 4) * wgt[i];
     }
-    auto store_out = [&](int tok, int hqx, float m_fin, float l_fin, const f32x4_t (&ov)[NB]) {
+    auto store_out = [&](int tok, int hqx, float m_fin, float l_fin, const f32x4_t (&ov)[NB]) {   // (m_fin, l_fin): the row's FINAL pair - the sink's place
+      const float sink_w = p.sinks ? fold_sink<true>(m_fin, l_fin, p.sinks[hqx]) : 1.0f;
       if (p.lse && grp == 0 && wave_in_wg == 0)
         p.lse[(int64_t)tok * p.lse_stride_token + hqx] = l_fin > 0.0f ? (m_fin + __builtin_amdgcn_logf(l_fin)) * kLn2 : -INFINITY;
-      const float inv = l_fin > 0.0f ? v_scale / l_fin : 0.0f;              // "0 if the overall sum is 0" (:828)
+      const float inv = l_fin > 0.0f ? v_scale / l_fin * sink_w : 0.0f;     // "0 if the overall sum is 0" (:828)
       const int64_t o = (int64_t)tok * p.out_stride_token + (int64_t)hqx * p.out_stride_head;
 #pragma unroll
       for (int j = 0; j < NB; ++j) {
@@ -798,9 +799,11 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
 #pragma unroll
     for (int cg = 0; cg < NCG; ++cg) {
       if (!g_ok[cg]) continue;
+      // attention sink: this wave saw all the row's keys, (m_run, l_tot) is final (PACK: a column is a (token, head): its own head's sink)
+      const float sink_w = p.sinks ? fold_sink<true>(m_run[cg], l_tot[cg], p.sinks[hq[cg]]) : 1.0f;
       if (p.lse && grp == 0)   // m_run is the row max of the scaled scores in the log2 domain
         p.lse[(int64_t)token[cg] * p.lse_stride_token + hq[cg]] = l_tot[cg] > 0.0f ? (m_run[cg] + __builtin_amdgcn_logf(l_tot[cg])) * kLn2 : -INFINITY;
-      const float inv = l_tot[cg] > 0.0f ? v_scale / l_tot[cg] : 0.0f;
+      const float inv = l_tot[cg] > 0.0f ? v_scale / l_tot[cg] * sink_w : 0.0f;
       const int64_t o = (int64_t)token[cg] * p.out_stride_token + (int64_t)hq[cg] * p.out_stride_head;
 #pragma unroll
       for (int b = 0; b < DBLK; ++b)
@@ -905,9 +908,10 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
     fold(m_in, l_in, v_in);
   }
   if (gm_ok && sub == 0) {
+    const float sink_w = p.sinks ? fold_sink<true>(m_acc, l_acc, p.sinks[hqm]) : 1.0f;   // attention sink: after the last fold, by the one wave that merges
     if (p.lse && grp == 0)
       p.lse[(int64_t)tokm * p.lse_stride_token + hqm] = l_acc > 0.0f ? (m_acc + __builtin_amdgcn_logf(l_acc)) * kLn2 : -INFINITY;
-    const float inv = l_acc > 0.0f ? v_scale / l_acc : 0.0f;              // "0 if the overall sum is 0" (:828)
+    const float inv = l_acc > 0.0f ? v_scale / l_acc * sink_w : 0.0f;     // "0 if the overall sum is 0" (:828)
     const int64_t o = (int64_t)tokm * p.out_stride_token + (int64_t)hqm * p.out_stride_head;
 #pragma unroll
     for (int b = 0; b < DBLK; ++b)
@@ -1004,7 +1008,8 @@ __global__ __launch_bounds__(256) void reduce_splits_kernel(const DecodeArgs a) 
     l_all += red[rr][D + 1] * w;
     acc += *(const f32x4_t*)&red[rr][4 * col] * w;
   }
-  const float inv = l_all > 0.0f ? v_scale / l_all : 0.0f;  // "0 if the overall sum is 0" (:828)
+  const float sink_w = p.sinks ? fold_sink<true>(m_all, l_all, p.sinks[hq]) : 1.0f;   // attention sink: the partials are sink-free, the row's pair is final here
+  const float inv = l_all > 0.0f ? v_scale / l_all * sink_w : 0.0f;  // "0 if the overall sum is 0" (:828)
   if (p.lse && col == 0) p.lse[(int64_t)ri.token * p.lse_stride_token + hq] = l_all > 0.0f ? (m_all + __builtin_amdgcn_logf(l_all)) * kLn2 : -INFINITY;
   uint16_t* op = (uint16_t*)p.out + (int64_t)ri.token * p.out_stride_token + (int64_t)hq * p.out_stride_head;
   if (4 * col < a.d_valid) *(u32x2_t*)(op + 4 * col) = u32x2_t{mma<T>::pack2(acc[0] * inv, acc[1] * inv), mma<T>::pack2(acc[2] * inv, acc[3] * inv)};

@@ -132,7 +132,9 @@ __global__ __launch_bounds__(64) void generic_attn_kernel(const GenericArgs a) {
     }
   }
 
-  const float inv_l = (l > 0.0f) ? 1.0f / l : 0.0f;
+  // attention sink: one more term of the denominator, here where (m, l) is final (fold_sink, common.h)
+  const float sink_w = p.sinks ? fold_sink<false>(m, l, p.sinks[head]) : 1.0f;
+  const float inv_l = (l > 0.0f) ? sink_w / l : 0.0f;
   const int64_t o_off = (int64_t)token * p.out_stride_token + (int64_t)head * p.out_stride_head;
 #pragma unroll
   for (int i = 0; i < kDRegs; ++i) {

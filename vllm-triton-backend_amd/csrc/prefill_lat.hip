@@ -588,9 +588,11 @@ __global__ __launch_bounds__(128 * NKQ, NKQ == 2 ? 2 : 1) void prefill_lat_kerne
     }
     const bool ok = row_ok[cg];
     const int tok = q_start + tok_local[cg], hqx = hq[cg];
+    // attention sink: the key parts have met, (m_all, l_all) is the row's final pair (every wave of the row half folds the same)
+    const float sink_w = (p.sinks && ok) ? fold_sink<true>(m_all, l_all, p.sinks[hqx]) : 1.0f;
     if (p.lse && ok && grp == 0 && kh == 0)
       p.lse[(int64_t)tok * p.lse_stride_token + hqx] = l_all > 0.0f ? (m_all + __builtin_amdgcn_logf(l_all)) * kLatLn2 : -INFINITY;
-    const float inv = l_all > 0.0f ? v_sc / l_all : 0.0f;        // a row that sees no key: 0 (:494)
+    const float inv = l_all > 0.0f ? v_sc / l_all * sink_w : 0.0f;   // a row that sees no key: 0 (:494)
     uint16_t* op = (uint16_t*)p.out + (int64_t)tok * p.out_stride_token + (int64_t)hqx * p.out_stride_head + 4 * grp;
 #pragma unroll
     for (int j = 0; j < NB; ++j) {

@@ -565,9 +565,11 @@ __global__ __launch_bounds__(256, D <= 128 ? 2 : 1) void prefill_mfma_kernel(con
 
   // ---- epilogue: O = O^T / l, lane (qr, half) register r of block b <-> d = 32b + (r&3) + 8(r>>2) + 4half
   l_run += lane_xor32(l_run);
+  // attention sink: the row's (m_run, l_run) is final here (a key-split launch is handed sinks == NULL: its merge adds the term)
+  const float sink_w = (p.sinks && row_ok) ? fold_sink<true>(m_run, l_run, p.sinks[hq]) : 1.0f;
   if (lse_base && row_ok && half == 0)    // m_run: row max of the scaled scores in the log2 domain
     lse_base[(int64_t)(q_start + tok_local) * p.lse_stride_token + hq] = l_run > 0.0f ? (m_run + __builtin_amdgcn_logf(l_run)) * 0.6931471805599453f : -INFINITY;
-  const float inv = (row_ok && l_run > 0.0f) ? v_scale / l_run : 0.0f;
+  const float inv = (row_ok && l_run > 0.0f) ? v_scale / l_run * sink_w : 0.0f;
   // O leaves through LDS as whole rows, 16 bytes per lane, nontemporal (see prefill_dma_kernel's epilogue); the
   // 8-byte pieces of the accumulator layout go out directly only when the output rows are not 16-byte aligned.
   const bool wide_store = (((uintptr_t)out_base & 15) == 0) && (p.out_stride_token % 8 == 0) && (p.out_stride_head % 8 == 0);
@@ -1235,9 +1237,12 @@ __global__ __launch_bounds__(NW * 64, (NW == 4 && D == 128) ? 2 : 1) void prefil
   }
 #endif
   l_run += lane_xor32(l_run);
+  // attention sink: (m_ref, l_run) is the row's final pair - a sum relative to the reference, which the fold takes as it takes a maximum
+  // (a key-split launch is handed sinks == NULL: its merge adds the term)
+  const float sink_w = (p.sinks && row_ok) ? fold_sink<true>(m_ref, l_run, p.sinks[hq]) : 1.0f;
   if (lse_base && row_ok && half == 0)    // P = exp2(score - m_ref): the sum is relative to the reference max
     lse_base[(int64_t)(q_start + tok_local) * p.lse_stride_token + hq] = l_run > 0.0f ? (m_ref + __builtin_amdgcn_logf(l_run)) * 0.6931471805599453f : -INFINITY;
-  const float inv = (row_ok && l_run > 0.0f) ? 1.0f / l_run : 0.0f;
+  const float inv = (row_ok && l_run > 0.0f) ? sink_w / l_run : 0.0f;
   // O leaves through LDS: a lane owns 8-byte pieces of one row (the accumulator layout), which as global stores
   // touch 32 rows per instruction. Each wave parks its 32 rows in its own corner of the (now idle) stages and
   // writes them out as whole 256-byte rows, 16 bytes per lane. (Nontemporal stores of the 8-byte pieces were
@@ -1470,7 +1475,9 @@ __global__ __launch_bounds__(256) void merge_key_splits_kernel(const MergeArgs a
       }
     }
   }
-  const float inv = den > 0.0f ? 1.0f / den : 0.0f;        // a row no split saw a key for: 0 (and lse -inf)
+  // attention sink: the key splits' partials are sink-free (launch_prefill_ws), the term enters the merged pair, once
+  const float sink_w = p.sinks ? fold_sink<false>(m, den, p.sinks[hq]) : 1.0f;
+  const float inv = den > 0.0f ? sink_w / den : 0.0f;      // a row no split saw a key for: 0 (and lse -inf, or its sink)
   pu32x4_t o;
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = pmma<T>::pack2(acc[2 * e] * inv, acc[2 * e + 1] * inv);
@@ -1733,6 +1740,7 @@ int launch_prefill_ws(const mi355_attn_params& p, void* ws, size_t ws_bytes, hip
   pp.out_stride_head = p.head_size;
   pp.lse = (float*)((char*)ws + lay.lse_off);
   pp.lse_stride_token = p.num_q_heads;
+  pp.sinks = nullptr;                               // partials stay sink-free: the merge below adds the row's sink, once
   const KeySplitCtx ks = {plan.splits, plan.tiles_per_split, plan.wide, lay.out_split_stride, lay.lse_split_stride};
   int rc = launch_prefill(pp, stream, &ks, counters);
   if (rc != MI355_OK) return rc;

@@ -459,7 +459,9 @@ __device__ __forceinline__ void pw_row_fallback(ArgPtr kp, const int32_t* bt, co
     a1 = a1 * alpha + pw_lo<T>(pr) * pw_hi<T>(vw);
     m = mn;
   }
-  const float inv = l > 0.0f ? v_sc / l : 0.0f;
+  const float* const sinks = kp->p.sinks;                   // attention sink: the row's own (m, l) is final here too
+  const float sink_w = sinks ? fold_sink<true>(m, l, sinks[hq]) : 1.0f;
+  const float inv = l > 0.0f ? v_sc / l * sink_w : 0.0f;
   if (act) *(uint32_t*)(out_base + (int64_t)token * kp->p.out_stride_token + (int64_t)hq * kp->p.out_stride_head + dl) = pw_pack<T>(a0 * inv, a1 * inv);
   if (lse_base && lane == 0)
     lse_base[(int64_t)token * kp->p.lse_stride_token + hq] = l > 0.0f ? (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f : -INFINITY;
@@ -1641,6 +1643,10 @@ __global__ __launch_bounds__(256, 1) void prefill_pw_kernel(const PwArgs a) {
     const uint32_t st_b = (uint32_t)sa.out_st * 2u, sh_b = (uint32_t)sa.out_sh * 2u;
     const uint32_t tok_left = (uint32_t)min(I.q_len - I.tok0, sa.BQ);   // tokens of this block inside the sequence
     const float v_sc8 = (KV8 && kp->p.v_scale != nullptr) ? kp->p.v_scale[0] : 1.0f;
+    // attention sinks: a row's pair (reference, sum) is final in this epilogue - its sink joins the sum here, outside the tile
+    // loop and its tables (a key-split launch is handed NULL: its partials stay sink-free and the merge adds the term). The
+    // range checks below keep looking at the sum of the keys alone.
+    const float* const sinks = kp->p.sinks;
     bool bad[2];                                 // the row left the range the reference-0 arithmetic is good for
     bool bad16[2][2] = {{false, false}, {false, false}};   // M16: per (sub-block, row tile)
     if constexpr (M16) {
@@ -1666,9 +1672,17 @@ __global__ __launch_bounds__(256, 1) void prefill_pw_kernel(const PwArgs a) {
           const float l = L16[x][rt][0];                     // the row's whole sum (of P as P.V saw it: rounded to bf16)
           int tok_local, hq;
           const bool row_ok = row_of(I, 2 * x + rt, tok_local, hq);
+          float l_fin = l, sink_w = 1.0f, m_fin = 0.0f;
+          const bool sunk = __builtin_expect(sinks != nullptr, 0) && row_ok;
+          if (sunk) {                                      // the sum is relative to -R (+ A): that reference stands where a running maximum would
+            m_fin = sc_a - (AL ? al_base[x][rt] + al_sl[x][rt] * (float)I.ctx_len : R16[x][rt][0]);
+            sink_w = fold_sink<true>(m_fin, l_fin, sinks[hq]);
+          }
           if (I.lse_base && row_ok && g4o == 0)
-            I.lse_base[(int64_t)(I.q_start + tok_local) * sa.lse_st + hq] = l > 0.0f ? (__builtin_amdgcn_logf(l) - (AL ? al_base[x][rt] + al_sl[x][rt] * (float)I.ctx_len : R16[x][rt][0]) + sc_a) * 0.6931471805599453f : -INFINITY;   // P = 2^(score + R) (SC: 2^(capped score - A + R); AL: the bias as the reference counts it, from the context's end)
-          float inv = (row_ok && l > 0.0f) ? __builtin_amdgcn_rcpf(l) : 0.0f;   // (1 ulp: the output is rounded to 16 bits next)
+            I.lse_base[(int64_t)(I.q_start + tok_local) * sa.lse_st + hq] = sunk ? (l_fin > 0.0f ? (m_fin + __builtin_amdgcn_logf(l_fin)) * 0.6931471805599453f : -INFINITY)
+                : l > 0.0f ? (__builtin_amdgcn_logf(l) - (AL ? al_base[x][rt] + al_sl[x][rt] * (float)I.ctx_len : R16[x][rt][0]) + sc_a) * 0.6931471805599453f : -INFINITY;   // P = 2^(score + R) (SC: 2^(capped score - A + R); AL: the bias as the reference counts it, from the context's end)
+          float inv = (row_ok && l_fin > 0.0f) ? __builtin_amdgcn_rcpf(l_fin) : 0.0f;   // (1 ulp: the output is rounded to 16 bits next)
+          if (sunk) inv *= sink_w;
           if constexpr (KV8) inv *= v_sc8;                 // fp8 cache: V was widened unscaled
           l2[rt] = l; ok2[rt] = row_ok;
           if (__builtin_expect(wide_store, 1)) {
@@ -1725,9 +1739,13 @@ __global__ __launch_bounds__(256, 1) void prefill_pw_kernel(const PwArgs a) {
       l += lane_xor32(l);
       int tok_local, hq;
       const bool row_ok = row_of(I, sb, tok_local, hq);
+      float l_fin = l, sink_w = 1.0f, m_fin = 0.0f;                                   // the reference is 0
+      const bool sunk = __builtin_expect(sinks != nullptr, 0) && row_ok;
+      if (sunk) sink_w = fold_sink<true>(m_fin, l_fin, sinks[hq]);
       if (I.lse_base && row_ok && half == 0)    // P = exp2(score): ln of the sum is the lse
-        I.lse_base[(int64_t)(I.q_start + tok_local) * sa.lse_st + hq] = l > 0.0f ? __builtin_amdgcn_logf(l) * 0.6931471805599453f : -INFINITY;
-      const float inv = (row_ok && l > 0.0f) ? __builtin_amdgcn_rcpf(l) : 0.0f;   // (1 ulp: the output is rounded to 16 bits next)
+        I.lse_base[(int64_t)(I.q_start + tok_local) * sa.lse_st + hq] = l_fin > 0.0f ? (m_fin + __builtin_amdgcn_logf(l_fin)) * 0.6931471805599453f : -INFINITY;
+      float inv = (row_ok && l_fin > 0.0f) ? __builtin_amdgcn_rcpf(l_fin) : 0.0f;   // (1 ulp: the output is rounded to 16 bits next)
+      if (sunk) inv *= sink_w;
       float amax = 0.0f;
       if (__builtin_expect(wide_store, 1)) {
         // the sub-block leaves as whole 256-byte rows, 16 bytes per lane (a lane's own 8-byte pieces touch 32 rows per

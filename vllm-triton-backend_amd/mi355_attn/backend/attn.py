@@ -217,6 +217,7 @@ class MI355AttentionImpl(AttentionImpl):
         attn_type: AttentionType = AttentionType.DECODER,
         kv_sharing_target_layer_name: Optional[int] = None,
         use_irope: bool = False,
+        sinks: Optional[torch.Tensor] = None,
     ) -> None:
         if blocksparse_params is not None:
             raise ValueError("MI355Attention does not support block-sparse attention.")
@@ -240,6 +241,12 @@ class MI355AttentionImpl(AttentionImpl):
         self.use_irope = use_irope
         self.num_queries_per_kv = self.num_heads // self.num_kv_heads
         self._q_scale_checked = False
+        # attention sinks (gpt-oss): one learned logit per query head, handed over by vLLM as a parameter of the layer
+        if sinks is not None:
+            assert sinks.shape[0] == num_heads, (
+                f"Sinks must have the same number of heads as the number of heads in the layer. Sinks shape: {sinks.shape}, num_heads: {num_heads}.")
+        self.sinks = sinks
+        self._sinks_dev: Optional[torch.Tensor] = None
 
         MI355AttentionBackend.validate_head_size(head_size)
 
@@ -294,7 +301,8 @@ class MI355AttentionImpl(AttentionImpl):
         # wave that owns a sequence's last tile stores the new token's K/V row into its page and attends over it
         # (the op falls back to the two calls below when the fused kernel does not serve the shape).
         # vLLM's slot_mapping of such a step points at position seq_len - 1 of each sequence, which is where the kernel writes.
-        plain = self.alibi_slopes is None and self.sliding_window == (-1, -1) and not self.logits_soft_cap
+        # (a layer with sinks always takes the two calls at the end: the fused cache writes carry no sinks)
+        plain = self.alibi_slopes is None and self.sliding_window == (-1, -1) and not self.logits_soft_cap and self.sinks is None
         if (attn_metadata.max_query_len == 1 and plain and self.kv_sharing_target_layer_name is None
                 and not (self.use_irope and attn_metadata.local_attn_metadata is not None) and _FUSED_DECODE_WRITE):
             q = query[:num_actual_tokens]
@@ -354,6 +362,9 @@ class MI355AttentionImpl(AttentionImpl):
         if self.alibi_slopes is not None and (self._alibi_dev is None or self._alibi_dev.device != query.device):
             self._alibi_dev = self.alibi_slopes.to(query.device)
 
+        if self.sinks is not None and (self._sinks_dev is None or self._sinks_dev.device != query.device):
+            self._sinks_dev = self.sinks.detach().to(device=query.device, dtype=torch.float32).contiguous()
+
         q = query[:num_actual_tokens]
         out = output[:num_actual_tokens]
         if out.dim() == 2:
@@ -365,5 +376,5 @@ class MI355AttentionImpl(AttentionImpl):
         torch.ops.mi355_attn.unified_attention(
             q, key_cache, value_cache, out, cu_seqlens_q, int(max_seqlen_q), seqused_k, int(max_seqlen_k), float(self.scale),
             int(self.sliding_window[0]), int(self.sliding_window[1]), block_table, float(self.logits_soft_cap), layer._k_scale, layer._v_scale,
-            self._alibi_dev, self.kv_cache_dtype, int(getattr(attn_metadata, "decode_rows_hint", 0)))
+            self._alibi_dev, self.kv_cache_dtype, int(getattr(attn_metadata, "decode_rows_hint", 0)), self._sinks_dev)
         return output

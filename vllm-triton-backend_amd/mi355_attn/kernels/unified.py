@@ -35,7 +35,7 @@ def fill_attn_params(
     block_table, softcap, k_descale, v_descale, alibi_slopes, force_selection,
     k_new=None, v_new=None, skip_decodes=False, only_decodes=False, num_segments=0,
     legacy_v0_layout=False, lse=None, write_new_kv=False, non_causal=False, slot_mapping=None, new_kv_all_rows=False,
-    decode_rows_hint=0,
+    decode_rows_hint=0, sinks=None,
 ):
     """Build the C struct. Returns (params, keepalive) — keepalive holds temporaries whose device
     memory the struct points to."""
@@ -65,6 +65,16 @@ def fill_attn_params(
         alibi_slopes = alibi_slopes.contiguous()
         keep.append(alibi_slopes)
         p.alibi_slopes = alibi_slopes.data_ptr()
+    if sinks is not None:
+        # attention sinks: fp32 [Hq], one logit per query head in the natural-log domain of the scaled scores
+        assert sinks.shape == (q.shape[1],), "Sinks must be num_query_heads size"
+        if sinks.dtype != torch.float32:
+            sinks = sinks.to(torch.float32)
+        if sinks.device != q.device:
+            sinks = sinks.to(q.device)
+        sinks = sinks.contiguous()
+        keep.append(sinks)
+        p.sinks = sinks.data_ptr()
     ks, vs = _scalar_tensor(k_descale, q.device), _scalar_tensor(v_descale, q.device)
     keep += [ks, vs]
     p.k_scale, p.v_scale = _lib.ptr(ks), _lib.ptr(vs)
@@ -141,6 +151,49 @@ def launch(p, device: torch.device, entry: str = "mi355_unified_attention") -> N
     _lib.check(rc, entry)
 
 
+def unified_attention_with_sinks(
+    q,
+    k,
+    v,
+    out,
+    cu_seqlens_q,
+    max_seqlen_q,
+    seqused_k,
+    max_seqlen_k,
+    avg_seqlen_q,
+    avg_seqlen_k,
+    softmax_scale,
+    causal,
+    window_size,
+    block_table,
+    softcap,
+    q_descale,
+    k_descale,
+    v_descale,
+    alibi_slopes=None,
+    force_selection=None,  # None, 2, 3 to select kernel (9: generic correctness kernel)
+    softmax_lse=None,      # extension: float32 [num_tokens, num_heads], receives log(sum(exp(scores))) per row
+    decode_rows_hint=0,    # extension: query tokens of this step's decode rows when the caller knows (1 + speculative drafts); 0 = library picks
+    sinks=None,            # attention sinks: float32 [num_heads], one logit per query head that joins every row's softmax denominator (and softmax_lse)
+):
+    """`unified_attention` (below) with one more trailing argument, `sinks`: the op's parameter list is the reference's plus
+    the two extensions recorded for it, so attention sinks - which the reference does not have - come in through this name."""
+    assert causal, "Only causal attention is supported"
+    assert q_descale is None, "Q scales not supported"
+    block_size = v.shape[1]
+    assert q.element_size() >= 2 or block_size >= 32, "Block size must be at least 32 for fp8"
+    if not q.is_cuda:
+        raise RuntimeError("mi355_attn.unified_attention needs tensors on an MI355X (cuda/hip) device; there is no CPU path")
+    p, keep = fill_attn_params(
+        q, k, v, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, softmax_scale, window_size,
+        block_table, softcap, k_descale, v_descale, alibi_slopes, force_selection, lse=softmax_lse, decode_rows_hint=decode_rows_hint,
+        sinks=sinks,
+    )
+    launch(p, q.device)
+    del keep
+    return None
+
+
 def unified_attention(
     q,
     k,
@@ -168,19 +221,9 @@ def unified_attention(
     """Causal paged attention over vLLM block tables; writes `out` in place and returns None, as
     the reference does. `avg_seqlen_q/k` only fed the reference's autotuner keys
     (triton_unified_attention.py:878-881) and are accepted and ignored."""
-    assert causal, "Only causal attention is supported"
-    assert q_descale is None, "Q scales not supported"
-    block_size = v.shape[1]
-    assert q.element_size() >= 2 or block_size >= 32, "Block size must be at least 32 for fp8"
-    if not q.is_cuda:
-        raise RuntimeError("mi355_attn.unified_attention needs tensors on an MI355X (cuda/hip) device; there is no CPU path")
-    p, keep = fill_attn_params(
-        q, k, v, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, softmax_scale, window_size,
-        block_table, softcap, k_descale, v_descale, alibi_slopes, force_selection, lse=softmax_lse, decode_rows_hint=decode_rows_hint,
-    )
-    launch(p, q.device)
-    del keep
-    return None
+    return unified_attention_with_sinks(q, k, v, out, cu_seqlens_q, max_seqlen_q, seqused_k, max_seqlen_k, avg_seqlen_q, avg_seqlen_k, softmax_scale, causal,
+                                        window_size, block_table, softcap, q_descale, k_descale, v_descale, alibi_slopes, force_selection, softmax_lse,
+                                        decode_rows_hint, None)
 
 
 def decode_attention_and_cache_write(q, key, value, k_cache, v_cache, out, seqused_k, max_seqlen_k, softmax_scale, block_table,

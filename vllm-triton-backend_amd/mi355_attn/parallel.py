@@ -116,7 +116,8 @@ def shard_batch(rank: int, world_size: int, q, k_cache, v_cache, cu_seqlens_q, s
 
 def shard_kv_heads(rank: int, world_size: int, q, k_cache, v_cache):
     """KV-head sharding (tensor-parallel layout): returns this rank's views (q_r, k_cache_r, v_cache_r)
-    and the query-head slice it owns."""
+    and the query-head slice it owns. Per-query-head tensors of the call (`alibi_slopes`, `sinks`) are sliced by the caller
+    with that same slice: `sinks[qs]`."""
     Hq, Hk = q.shape[1], k_cache.shape[2]
     if Hk % world_size != 0:
         raise ValueError(f"num_kv_heads {Hk} is not divisible by world size {world_size}")
