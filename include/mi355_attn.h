@@ -26,9 +26,15 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 700 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 800 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.8.0  No change to the structs or the entry points. decode_rows_hint now reaches 64 / G: a hint above what two column
+ *          groups hold (32 / G) and up to pow2_floor(64 / G) sends rows of up to that many tokens to the decode kernels'
+ *          four-column-group form (mi355_last_kernel(): decode_splitkv_pack4[_fp8] / decode_single_pack4[_fp8]) - a step whose
+ *          every sequence has at most `hint` tokens in one launch, a mixed step's such rows in its decode launch. Before, such
+ *          a hint was ignored (the prefill kernels served those rows). Without a hint, or with one that two groups hold,
+ *          dispatch, kernel names and workspace sizes are those of 0.7.0.
  *   0.7.0  Attention sinks. mi355_attn_params grew at its END (sinks): zero the struct before filling it and nothing changes -
  *          a call with sinks == NULL computes what 0.6.2 computed, bit for bit, on the same kernel with the same workspace.
  *          With sinks every kernel family adds the row's sink to its softmax denominator and to lse (see the field); dispatch,
@@ -231,8 +237,12 @@ typedef struct mi355_attn_params {
   /* library version >= 0.5.0. A step that mixes prefills with shorter rows is served by two launches, and sequences of
    * up to N query tokens are the decode launch's. 0: the library picks N = 16 / G (what one column group of the packed
    * decode kernel holds - a one-token row costs nothing extra there). A caller that KNOWS its decode rows carry more
-   * tokens (speculative decoding with k drafts: 1 + k) says so here and gets N = that, up to 32 / G (two column groups;
-   * ignored where they do not apply: features, head size 256, more). Host-known, so capture-stable. */
+   * tokens (speculative decoding with k drafts: 1 + k) says so here and gets N = that, up to 32 / G (two column groups)
+   * and - library version >= 0.8.0 - up to 64 / G (four column groups, rounded down to a power of two; taken only when the hint
+   * exceeds what two groups hold). Two and four groups need plain causal attention (no window / soft-cap / ALiBi), G <= 16,
+   * a flash-layout cache, head size 64 or 128 and no write_new_kv; a hint is ignored where they do not apply. With a hint of
+   * four groups' range a step whose every sequence has at most that many tokens is ONE decode launch. Host-known, so
+   * capture-stable. */
   int32_t decode_rows_hint;
 
   /* library version >= 0.7.0 (not in the reference's unified_attention; vLLM hands `sinks` to the attention implementation,

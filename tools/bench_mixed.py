@@ -36,8 +36,9 @@ HQ, HK = 32, 8
 WINDOW = 0          # sliding window (keys), 0 = none
 
 
-def run(qlens, kvlens, dev, iters=10):
-    Hq, Hk, D, page = HQ, HK, 128, 16
+def run(qlens, kvlens, dev, iters=10, D=128, hint=0, sinks=False, fp8=False):
+    """(D / hint / sinks / fp8: head size, decode_rows_hint, a per-head sink ramp, an fp8 e4m3 cache with scale 0.5)"""
+    Hq, Hk, page = HQ, HK, 16
     S, T = len(qlens), sum(qlens)
     pps = [(n + page - 1) // page for n in kvlens]
     nb = sum(pps) + 8
@@ -55,7 +56,11 @@ def run(qlens, kvlens, dev, iters=10):
     cu = cu.to(dev)
     sl = torch.tensor(kvlens, dtype=torch.int32, device=dev)
     out = torch.empty_like(q)
-    p, keep = ua.fill_attn_params(q, k, v, out, cu, max(qlens), sl, max(kvlens), 1 / math.sqrt(D), (WINDOW - 1, 0) if WINDOW else (-1, -1), bt, 0.0, None, None, None, None)
+    kvs = torch.tensor([0.5], dtype=torch.float32, device=dev) if fp8 else None
+    if fp8:
+        k, v = (k.float() / 0.5).to(torch.float8_e4m3fn), (v.float() / 0.5).to(torch.float8_e4m3fn)
+    p, keep = ua.fill_attn_params(q, k, v, out, cu, max(qlens), sl, max(kvlens), 1 / math.sqrt(D), (WINDOW - 1, 0) if WINDOW else (-1, -1), bt, 0.0, kvs, kvs, None, None,
+                                  decode_rows_hint=hint, sinks=torch.linspace(-8.0, 8.0, Hq, device=dev) if sinks else None)
     for _ in range(3):
         ua.launch(p, dev)
     torch.cuda.synchronize()
@@ -68,7 +73,7 @@ def run(qlens, kvlens, dev, iters=10):
     ts.sort()
     t = ts[len(ts) // 2]
     flops = sum(4 * D * Hq * (ql * (kl - ql) + ql * (ql + 1) / 2) for ql, kl in zip(qlens, kvlens))
-    byts = sum(kl * Hk * D * 4 for kl in kvlens) + 2 * T * Hq * D * 2
+    byts = sum(kl * Hk * D * (2 if fp8 else 4) for kl in kvlens) + 2 * T * Hq * D * 2
     return t, flops, byts, _lib.last_kernel()
 
 

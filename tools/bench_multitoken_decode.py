@@ -3,7 +3,10 @@
 context): the packed decode kernels (several tokens of a sequence in one wave's matrix columns) against the former
 route (the prefill kernels), same tensors. MI355_DECODE_PACK is the library's A/B switch (0: off, 1: one column group only), read once per process:
 the tool runs each setting in a child process of its own (--pack).
-  python tools/bench_multitoken_decode.py [--hq 32 --hk 8]"""
+  python tools/bench_multitoken_decode.py [--hq 32 --hk 8]
+--g8 adds the G = 8 verification rows (Hq 64 / Hk 8) that only four column groups hold, each with and without
+decode_rows_hint = 8 (without it the prefill kernels serve them): 64 x 8 and 64 x 6 tokens over 8192 keys at head size 128,
+64 x 8 at head size 64 with sinks, 64 x 8 over an fp8 e4m3 cache."""
 import argparse
 import os
 
@@ -27,6 +30,7 @@ def main():
     ap.add_argument("--hq", type=int, default=32)
     ap.add_argument("--hk", type=int, default=8)
     ap.add_argument("--window", type=int, default=0)
+    ap.add_argument("--g8", action="store_true", help="the G = 8 legs of four column groups (Hq 64 / Hk 8, decode_rows_hint 8 against none)")
     ap.add_argument("--pack", default=None, help="(internal) run one setting of MI355_DECODE_PACK in this process and print raw rows")
     a = ap.parse_args()
     if a.pack is None:       # parent: one child per setting (the library reads the switch once), rows joined side by side
@@ -59,6 +63,18 @@ def main():
             t, fl, by, kern = bench_mixed.run([ql] * b, [kv] * b, dev, iters=a.iters)
             row.append(f"{'packed' if pack != '0' else 'former'} {t * 1e6:8.1f} us {by / t / 1e12:5.2f} TB/s {kern}")
         print(f"{sh:>14}: " + "   |   ".join(row), flush=True)
+    if a.g8 and a.pack != "0":
+        bench_mixed.HQ, bench_mixed.HK = 64, 8
+        print("# G = 8 (Hq 64 / Hk 8, bf16): decode_rows_hint 8 | no hint: median us, K/V stream rate of 8 TB/s, kernel")
+        for name, ql, kw in (("64x8x8192 D128", 8, {}), ("64x8x8192 D64 sinks", 8, dict(D=64, sinks=True)), ("64x6x8192 D128", 6, {}),
+                             ("64x8x8192 D128 fp8", 8, dict(fp8=True))):
+            row = []
+            for hint in (8, 0):
+                torch.manual_seed(0)
+                t, fl, by, kern = bench_mixed.run([ql] * 64, [8192] * 64, dev, iters=a.iters, hint=hint, **kw)
+                row.append(f"{t * 1e6:8.1f} us {by / 1e6:7.1f} MB {by / t / 8e12:5.2f} {kern}")
+            print(f"{name:>22}: " + "   |   ".join(row), flush=True)
+        bench_mixed.HQ, bench_mixed.HK = a.hq, a.hk
     # a step that mixes prefill chunks with multi-token decode rows: rows x tokens x keys + chunks x tokens (no context)
     for rows, ql, kv, chunks, cl in a.mixed:
         row = []

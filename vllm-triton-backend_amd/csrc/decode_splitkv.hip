@@ -181,13 +181,33 @@ __device__ __forceinline__ RowInfo row_info(const mi355_attn_params& p, int by_s
 // 380); partials and outputs are addressed per column (token, head).
 // PACK = 2: TWO column groups per wave (32 columns: twice the tokens per unit, or G up to 16) - the K / V fragments a
 // lane reads from LDS feed two matrix instructions, the score / softmax work per tile doubles (head sizes up to 128).
+// PACK = 4: FOUR column groups per work unit (64 columns: 64 / G tokens - a 1 + 7 token verification row at G = 8) on a PAIR
+// of waves, which is the whole workgroup. One wave cannot hold it at head size 128: O alone is 128 accumulators per lane, Q 64
+// and a tile in flight 64 more - written that way hipcc used all 512 registers, 1012 bytes of scratch per lane and hundreds
+// of accumulator-register moves per tile. So each wave of the pair owns TWO column groups (the register budget of PACK = 2)
+// and the pair shares every K/V tile: wave w fetches the tile's 16-key group w (K and V rows, half the loads of a PACK = 2
+// wave) and parks it in the pair's LDS tile, one barrier, then both waves read all 32 keys' fragments for their columns.
+// The sequence's K/V leaves HBM / L2 once per 64 columns. The LDS tile is double-buffered by tile parity, so ONE barrier per
+// tile orders both hazards: a wave that parks tile t + 1 has passed barrier t, which its partner reached only after its last
+// read of tile t - 1 (same buffer); tile t's readers and tile t + 1's writers use different buffers. Both waves run the same
+// tile range and leave early only on unit-wide conditions, so they meet at every barrier. Partials are merged by
+// reduce_splits_kernel (the in-kernel merge's ticket is per wave, and a unit is two waves here).
+// The kernel asks for two waves per SIMD (amdgpu_waves_per_eu below; the other forms keep the default - their code is the
+// same with and without the attribute): left alone hipcc took 220 VGPRs + 80 AGPRs at head size 128, one wave per SIMD with
+// every LDS / barrier / matrix latency exposed, and the form lost to the prefill kernels (64 x 8 tokens x 8192 keys at
+// G = 8: 480 us against 437); held to 256 registers it is 228 VGPRs, no AGPRs, no scratch, and 403 us.
 template <typename T, typename KVT, int D, int WAVES, bool FEAT, bool PAD, bool V0, int PACK = 0>
-__global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const DecodeArgs a) {
+__global__ __launch_bounds__(WAVES * 64) __attribute__((amdgpu_waves_per_eu(PACK == 4 ? 2 : 1))) void decode_splitkv_kernel(const DecodeArgs a) {
   static_assert(!V0 || (__is_same(T, KVT) && !PAD), "the v0 layout path serves same-type 16-bit caches of a built head size");
   static_assert(!PACK || (!PAD && !V0), "packed query tokens: a flash-layout cache of a built head size");
-  static_assert(PACK != 2 || !FEAT, "two column groups: plain attention only");
-  static_assert(PACK != 2 || D <= 128, "two column groups: O, Q and the K/V tiles in flight fit the register file up to head size 128");
-  constexpr int NCG = PACK == 2 ? 2 : 1;            // column groups (16 matrix columns each) per wave
+  static_assert(PACK < 2 || !FEAT, "two / four column groups: plain attention only");
+  static_assert(PACK < 2 || D <= 128, "two / four column groups: O, Q and the K/V tiles in flight fit the register file up to head size 128");
+  static_assert(PACK == 0 || PACK == 1 || PACK == 2 || PACK == 4, "column groups per wave");
+  constexpr bool PAIR = PACK == 4;                  // the workgroup is two waves that share one work unit's K/V tiles
+  static_assert(PAIR == (WAVES == 2), "four column groups: a workgroup of two waves; everything else: four independent waves");
+  constexpr int NCG = PACK >= 2 ? 2 : 1;            // column groups (16 matrix columns each) per wave
+  constexpr int NH = PAIR ? 1 : 2;                  // 16-key groups of a tile this wave fetches
+  constexpr int KROWS = PAIR ? 32 : 16;             // key rows of the K region in LDS (a pair: the whole tile)
   constexpr bool FP8 = !__is_same(T, KVT);
   // tiles in flight HBM -> VGPR per wave. Rounds 2-3 kept TWO fp8 tiles in flight (half the bytes of a 16-bit tile each);
   // re-measured in round 4 on the kernel as it is now (nt loads, hardware converts), ONE is 3 % faster wherever the fp8 kernel
@@ -206,22 +226,23 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
   constexpr int KSTEPS = D / 32;                    // MFMA k-steps of Q.K^T
   constexpr int DBLK = D / 16;                      // 16-wide output blocks of P.V
   constexpr int RSV0 = 80;                          // v0: bytes per d-row of the parked V tile (32 keys + pad)
-  constexpr int LDS_PER_WAVE = 16 * RS + (V0 ? D * RSV0 : 32 * RS);   // K: one 16-key group; V: two groups (or D rows of 32 keys)
+  constexpr int LDS_PER_WAVE = KROWS * RS + (V0 ? D * RSV0 : 32 * RS);   // K: one 16-key group (four column groups: two); V: two groups (or D rows of 32 keys)
   static_assert(NLD >= 1, "head size too small for the row-shaped load");
 
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const mi355_attn_params& p = a.p;
   const int lane = threadIdx.x & 63;
   const int wave_in_wg = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  char* k_lds = smem + wave_in_wg * LDS_PER_WAVE;
-  char* v_lds = k_lds + 16 * RS;
+  char* k_lds = smem + (PAIR ? 0 : wave_in_wg * LDS_PER_WAVE);    // (a pair: two tile buffers of LDS_PER_WAVE bytes, see tile_body)
+  char* v_lds = k_lds + KROWS * RS;
+  const int half = PAIR ? wave_in_wg : 0;           // a pair: this wave fetches 16-key group `half` and owns columns 32 * half ..
 
   // ---- which (unit, split, kv head) this wave owns (all wave-uniform) ----------------------------
   const int Hk = p.num_kv_heads;
   const bool tree = PACK == 0 && a.tree;
-  static_assert(WAVES == 4, "the two-level merge folds the four waves of a workgroup");
+  static_assert(WAVES == 4 || PACK, "the two-level merge folds the four waves of a workgroup");
   // (tree: the workgroup is (unit, group of four splits, KV head, query-head group) and its waves are the group's splits)
-  const int item = __builtin_amdgcn_readfirstlane(tree ? (int)blockIdx.x : (int)(blockIdx.x * WAVES + wave_in_wg));
+  const int item = __builtin_amdgcn_readfirstlane((tree || PAIR) ? (int)blockIdx.x : (int)(blockIdx.x * WAVES + wave_in_wg));
   // (the waves of one KV head's query-head groups are neighbours: they stream the same K/V pages through one L2)
   const int hitem = item % (Hk * a.qgroups);
   const int head = hitem / a.qgroups, qg = hitem % a.qgroups;
@@ -232,12 +253,12 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
   const int hq0 = head * a.group + 16 * qg;   // first query head of this wave
   const int G = min(16, a.group - 16 * qg);   // query heads of this wave
   const int g = lane & 15, grp = lane >> 4;
-  // PACK: column c = 16 * cg + g = (token tq of the unit's chunk, query head c % G)
+  // PACK: column c = 16 * cg + g (a pair: + 32 * half) = (token tq of the unit's chunk, query head c % G)
   int tq[NCG], hq[NCG];
   bool g_ok[NCG];
 #pragma unroll
   for (int cg = 0; cg < NCG; ++cg) {
-    const int c = 16 * cg + g;
+    const int c = 32 * half + 16 * cg + g;
     tq[cg] = PACK ? c / G : 0;
     hq[cg] = hq0 + c - tq[cg] * G;
     g_ok[cg] = PACK ? tq[cg] < a.pack_tokens : g < G;
@@ -401,14 +422,16 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
     int d0, d1;
     scalar_load4(bt, i0, i1, i0, i1, pg[0], pg[1], d0, d1);
   };
-  u32x4_t kreg[PF][2][NLD], vreg[PF][2][NLD];
-  auto issue_loads = [&](int tile, u32x4_t (&KR)[2][NLD], u32x4_t (&VR)[2][NLD]) {   // uses pg[] = this tile's pages
+  u32x4_t kreg[PF][NH][NLD], vreg[PF][NH][NLD];
+  auto issue_loads = [&](int tile, u32x4_t (&KR)[NH][NLD], u32x4_t (&VR)[NH][NLD]) {   // uses pg[] = this tile's pages
 #pragma unroll
-    for (int h = 0; h < 2; ++h) {
-      const int gi = min(tile * 2 + h, last_group);
+    for (int h = 0; h < NH; ++h) {
+      const int hh = PAIR ? half : h;                                       // (a pair: this wave's 16-key group of the tile)
+      const int page = PAIR ? (half ? pg[1] : pg[0]) : pg[h];
+      const int gi = min(tile * 2 + hh, last_group);
       const int slot0 = (gi << 4) & page_mask;
-      const kv_elem_t* kp = kbase + ((uint64_t)(uint32_t)pg[h] * a.k_page_stride + (uint32_t)slot0 * a.k_slot_stride);
-      const kv_elem_t* vp = vbase + ((uint64_t)(uint32_t)pg[h] * a.v_page_stride + (uint32_t)slot0 * a.v_slot_stride);
+      const kv_elem_t* kp = kbase + ((uint64_t)(uint32_t)page * a.k_page_stride + (uint32_t)slot0 * a.k_slot_stride);
+      const kv_elem_t* vp = vbase + ((uint64_t)(uint32_t)page * a.v_page_stride + (uint32_t)slot0 * a.v_slot_stride);
 #pragma unroll
       for (int i = 0; i < NLD; ++i) {
 #ifdef MI355_DECODE_PLAIN_LOADS
@@ -471,13 +494,19 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
 #pragma unroll
     for (int cg = 0; cg < NCG; ++cg) asm volatile("" : "+v"(qf[cg][c]));   // retire the Q loads before the loop (see prefill kernel)
 
-  auto tile_body = [&](int tile, u32x4_t (&KR)[2][NLD], u32x4_t (&VR)[2][NLD]) __attribute__((always_inline)) {
+  auto tile_body = [&](int tile, u32x4_t (&KR)[NH][NLD], u32x4_t (&VR)[NH][NLD]) __attribute__((always_inline)) {
     // ---- park the current tile's rows in LDS, then refill the registers with a later tile --------
-    u32x4_t kcur[2][NLD];
+    // (a pair: the tile buffer of this tile's parity, K rows 0 .. 31 then V rows 0 .. 31; this wave parks rows 16 * half ..)
+    char* const k_t = PAIR ? smem + ((tile - t0) & 1) * LDS_PER_WAVE : k_lds;
+    char* const v_t = PAIR ? k_t + KROWS * RS : v_lds;
+    u32x4_t kcur[NH][NLD];
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int h = 0; h < NH; ++h)
 #pragma unroll
-      for (int i = 0; i < NLD; ++i) kcur[h][i] = KR[h][i];
+      for (int i = 0; i < NLD; ++i) {
+        if constexpr (PAIR) park(k_t, 16 * half + ld_row[i], ld_piece[i], KR[h][i]);
+        else kcur[h][i] = KR[h][i];
+      }
     const bool tail = (tile * kTileKeys + kTileKeys > n_keys);
     if constexpr (!V0 && !FEAT && !PACK) {
       // Fused cache write (write_new_kv): the wave whose split ends at the sequence's last tile owns the key of the
@@ -516,10 +545,11 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
       }
     }
 #pragma unroll
-    for (int h = 0; h < 2; ++h)
+    for (int h0 = 0; h0 < NH; ++h0)
 #pragma unroll
       for (int i = 0; i < NLD; ++i) {
-        u32x4_t v = VR[h][i];
+        const int h = PAIR ? half : h0;
+        u32x4_t v = VR[h0][i];
         if constexpr (V0) {
           // the piece is 8 consecutive keys of row d: zero the keys past the sequence (stale slots), park d-major
           const int idx = lane + 64 * i, d_row = idx / 2, hf = idx % 2;
@@ -531,12 +561,12 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
               v[w] &= keep;
             }
           }
-          *(u32x4_t*)(v_lds + d_row * RSV0 + (h * 16 + hf * 8) * 2) = v;
+          *(u32x4_t*)(v_t + d_row * RSV0 + (h * 16 + hf * 8) * 2) = v;
         } else {
           // rows past the sequence hold stale cache contents: keep NaN/Inf out of 0 * V
           if (tail && (tile * kTileKeys + h * 16 + ld_row[i] >= n_keys)) v = u32x4_t{0, 0, 0, 0};
           if (PAD && ld_pad[i]) v = u32x4_t{0, 0, 0, 0};
-          park(v_lds, h * 16 + ld_row[i], ld_piece[i], v);
+          park(v_t, h * 16 + ld_row[i], ld_piece[i], v);
         }
       }
     if (tile + PF < t1) {
@@ -546,6 +576,22 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
 
     // ---- S^T = K . Q^T, one 16-key group at a time through the K buffer --------------------------
     f32x4_t s[NCG][2];
+    if constexpr (PAIR) {
+      // the partner's half of the tile is in LDS after the barrier (the only one of the tile, see the kernel's head)
+      __syncthreads();
+#pragma unroll
+      for (int h = 0; h < 2; ++h) {
+        u32x4_t kf[KSTEPS];
+#pragma unroll
+        for (int c = 0; c < KSTEPS; ++c) kf[c] = *(const u32x4_t*)(k_t + (h * 16 + g) * RS + c * 64 + grp * 16);
+#pragma unroll
+        for (int cg = 0; cg < NCG; ++cg) s[cg][h] = f32x4_t{0, 0, 0, 0};
+#pragma unroll
+        for (int c = 0; c < KSTEPS; ++c)
+#pragma unroll
+          for (int cg = 0; cg < NCG; ++cg) s[cg][h] = mma<T>::run(__builtin_bit_cast(s16x8_t, kf[c]), qf[cg][c], s[cg][h]);
+      }
+    } else
 #pragma unroll
     for (int h = 0; h < 2; ++h) {
 #pragma unroll
@@ -629,12 +675,12 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
       s16x4_t v0, v1;
       if constexpr (V0) {
         // d-major tile: lane (g, grp) is row d = 16b + g and takes keys 4grp .. 4grp+3 of each 16-key group as they lie
-        const char* va = v_lds + (16 * b + g) * RSV0 + (4 * grp) * 2;
+        const char* va = v_t + (16 * b + g) * RSV0 + (4 * grp) * 2;
         v0 = *(const s16x4_t*)va;
         v1 = *(const s16x4_t*)(va + 32);
       } else {
         const int q4 = g >> 2, pp = g & 3;
-        const char* va = v_lds + (grp * 4 + q4) * RS + (16 * b + 4 * pp) * 2;
+        const char* va = v_t + (grp * 4 + q4) * RS + (16 * b + 4 * pp) * 2;
         v0 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va));
         v1 = __builtin_amdgcn_ds_read_tr16_b64_v4i16((__attribute__((address_space(3))) s16x4_t*)(va + 16 * RS));
       }
@@ -826,7 +872,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
 #pragma unroll
   for (int cg = 0; cg < NCG; ++cg)
   if (g_ok[cg]) {
-    const uint32_t so = ((slot_of_col(16 * cg + g) + split) * SLOT) * 4u;
+    const uint32_t so = ((slot_of_col(32 * half + 16 * cg + g) + split) * SLOT) * 4u;
 #pragma unroll
     for (int b = 0; b < DBLK; ++b)
       __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4_t, o_acc[cg][b]), rsrc, so + (16 * b + 4 * grp) * 4, 0, 16);
@@ -834,7 +880,7 @@ __global__ __launch_bounds__(WAVES * 64) void decode_splitkv_kernel(const Decode
       // (PACK: a split whose tiles lie past a column's last key leaves that column an empty partial)
       __builtin_amdgcn_raw_buffer_store_b64(u32x2_t{__builtin_bit_cast(uint32_t, (PACK && !(l_tot[cg] > 0.0f)) ? -INFINITY : m_run[cg]), __builtin_bit_cast(uint32_t, l_tot[cg])}, rsrc, so + D * 4, 0, 16);
   }
-  if (!a.fused_merge) return;
+  if (PAIR || !a.fused_merge) return;     // (a pair's partials always meet in reduce_splits_kernel)
 
   // ---- in-kernel merge by the last-arriving split of this (unit, KV head) (reference: reduce_segments, :757-836)
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                       // every storing wave drains before it signals
@@ -1076,7 +1122,8 @@ static int query_head_groups(const mi355_attn_params& p) { return (p.num_q_heads
 // Multi-token decode steps on the PACK kernels: plain attention (no window / soft-cap / ALiBi), flash layout, a built
 // head size. One column group (16 matrix columns) per wave holds 16 / G tokens (G <= 8), two hold 32 / G (G <= 16,
 // head sizes up to 128), both rounded down to a power of two; one group is taken when the longest query fits it.
-// MI355_DECODE_PACK=0 switches packing off, =1 keeps it to one column group (A/B).
+// Four hold 64 / G tokens (G <= 16, head sizes up to 128) and are taken only with a decode_rows_hint that asks for them.
+// MI355_DECODE_PACK=0 switches packing off, =1 keeps it to one column group (A/B; four groups: call without the hint).
 static int pow2_floor_shift(int x) { return x < 1 ? -1 : 31 - __builtin_clz((unsigned)x); }
 // only_decodes = N > 1 (the decode launch of a mixed batch): the rows of sequences with up to N query tokens.
 static int pack_max_q(const mi355_attn_params& p) { return p.only_decodes > 1 ? p.only_decodes : p.max_seqlen_q; }
@@ -1092,6 +1139,13 @@ int decode_pack_groups(const mi355_attn_params& p) {
   static const char* const e = lab_env("MI355_DECODE_PACK");     // read once per process, like the other switches
   if (e && e[0] == '0') return 0;
   const bool one_ok = G <= 8, two_ok = G <= 16 && p.head_size <= 128 && !feat && !(e && e[0] == '1');
+  // Four column groups (64 / G tokens per unit) only on the caller's word - decode_rows_hint says that rows of up to that
+  // many tokens are verification rows over a long context, not short prompts - and only where two groups do not hold
+  // the longest row. All of it host-known: the plan and the workspace size are capture-stable.
+  const int hint = p.decode_rows_hint;
+  if (two_ok && hint > (1 << pow2_floor_shift(32 / G)) && hint <= (1 << pow2_floor_shift(64 / G)) &&
+      pack_max_q(p) > (1 << pow2_floor_shift(32 / G)) && pack_max_q(p) <= hint)
+    return 4;
   if (one_ok && (pack_max_q(p) <= (1 << pow2_floor_shift(16 / G)) || !two_ok)) return 1;
   return two_ok ? 2 : 0;
 }
@@ -1201,6 +1255,7 @@ static MergePlan plan_merge(const mi355_attn_params& p) {
   const int G = std::min(p.num_q_heads / p.num_kv_heads, 16) << ps, Gp = G <= 1 ? 1 : 1 << (32 - __builtin_clz((unsigned)(G - 1)));   // columns in use
   // (one column group of packed tokens: two trips at worst - a unit with every column in use - against a merge launch
   // over all token slots; units with fewer tokens walk their splits on more lanes, see the kernel)
+  if (pack == 4) return m;      // (a unit is a pair of waves there: no single last arriver, the merge launch folds its partials)
   const int one_trip = (pack == 2 ? 1 : pack == 1 ? 2 : 16 / Gp) * (D >= 128 ? 2 : 4);
   if (sp.num_splits <= one_trip) { m.flat = true; return m; }
   // Where the two-level merge pays (round 4, one box): a decode step of a few sequences planned for a long context - what a
@@ -1234,7 +1289,7 @@ size_t decode_workspace_bytes(const mi355_attn_params& p) {
 
 template <typename T, typename KVT, int D, bool FEAT, bool PAD, bool V0, int PACK = 0>
 static int launch_decode_t(const mi355_attn_params& p, void* ws, size_t ws_bytes, hipStream_t stream) {
-  constexpr int WAVES = 4;
+  constexpr int WAVES = PACK == 4 ? 2 : 4;      // (four column groups: the workgroup is the pair of waves of ONE work item)
   constexpr bool FP8 = !__is_same(T, KVT);
   DecodeArgs a;
   a.p = p;
@@ -1278,9 +1333,10 @@ static int launch_decode_t(const mi355_attn_params& p, void* ws, size_t ws_bytes
   const long units = decode_units(p);
   if (units == 0) return MI355_OK;
   const long items = units * sp.num_splits * p.num_kv_heads * a.qgroups;
-  const int grid = (int)((items + WAVES - 1) / WAVES);      // (tree: num_splits is a multiple of four - one workgroup per group of four)
+  const int grid = PACK == 4 ? (int)items : (int)((items + WAVES - 1) / WAVES);      // (tree: num_splits is a multiple of four - one workgroup per group of four)
   if (PACK && (a.group << a.pack_shift) > 16 * PACK) { set_error("decode: packed columns exceed the wave's"); return MI355_ERR_UNSUPPORTED; }
-  const size_t lds = (size_t)WAVES * (16 * (D * 2 + 32) + (V0 ? D * 80 : 32 * (D * 2 + 32)));
+  // (four column groups: two buffers of a whole tile - 32 K rows, 32 V rows - shared by the pair)
+  const size_t lds = (size_t)WAVES * ((PACK == 4 ? 32 : 16) * (D * 2 + 32) + (V0 ? D * 80 : 32 * (D * 2 + 32)));
   hipLaunchKernelGGL((decode_splitkv_kernel<T, KVT, D, WAVES, FEAT, PAD, V0, PACK>), dim3(grid), dim3(WAVES * 64), lds, stream, a);
   int rc = check_hip(hipGetLastError(), "decode_splitkv_kernel launch");
   if (rc != MI355_OK) return rc;
@@ -1295,6 +1351,7 @@ static int launch_decode_t(const mi355_attn_params& p, void* ws, size_t ws_bytes
     set_kernel_name(V0 ? (sp.num_splits > 1 ? "decode_splitkv_v0" : "decode_single_v0")
                        : PACK == 1 ? (sp.num_splits > 1 ? (FP8 ? "decode_splitkv_pack_fp8" : "decode_splitkv_pack") : (FP8 ? "decode_single_pack_fp8" : "decode_single_pack"))
                        : PACK == 2 ? (sp.num_splits > 1 ? (FP8 ? "decode_splitkv_pack2_fp8" : "decode_splitkv_pack2") : (FP8 ? "decode_single_pack2_fp8" : "decode_single_pack2"))
+                       : PACK == 4 ? (sp.num_splits > 1 ? (FP8 ? "decode_splitkv_pack4_fp8" : "decode_splitkv_pack4") : (FP8 ? "decode_single_pack4_fp8" : "decode_single_pack4"))
                        : sp.num_splits > 1 ? (FP8 ? "decode_splitkv_fp8" : "decode_splitkv") : (FP8 ? "decode_single_fp8" : "decode_single"));
   return rc;
 }
@@ -1303,6 +1360,23 @@ static int launch_decode_t(const mi355_attn_params& p, void* ws, size_t ws_bytes
 // DECODE_TU = 1), so that the library's objects keep compiling side by side in about a minute each.
 template <typename T, typename KVT, int D>
 int launch_decode_pack(const mi355_attn_params& p, void* ws, size_t ws_bytes, hipStream_t stream, bool feat, int groups);
+
+// (and the four-column-group ones in a third: decode_splitkv_pack4.hip, DECODE_TU = 2)
+template <typename T, typename KVT, int D>
+int launch_decode_pack4(const mi355_attn_params& p, void* ws, size_t ws_bytes, hipStream_t stream);
+
+#if DECODE_TU == 2
+template <typename T, typename KVT, int D>
+int launch_decode_pack4(const mi355_attn_params& p, void* ws, size_t ws_bytes, hipStream_t stream) {
+  return launch_decode_t<T, KVT, D, false, false, false, 4>(p, ws, ws_bytes, stream);
+}
+#define MI355_PACK4_INST(T, KVT) \
+  template int launch_decode_pack4<T, KVT, 64>(const mi355_attn_params&, void*, size_t, hipStream_t); \
+  template int launch_decode_pack4<T, KVT, 128>(const mi355_attn_params&, void*, size_t, hipStream_t);
+MI355_PACK4_INST(bf16_t, bf16_t) MI355_PACK4_INST(bf16_t, e4m3_t) MI355_PACK4_INST(bf16_t, e5m2_t)
+MI355_PACK4_INST(f16_t, f16_t) MI355_PACK4_INST(f16_t, e4m3_t) MI355_PACK4_INST(f16_t, e5m2_t)
+#undef MI355_PACK4_INST
+#endif
 
 #if DECODE_TU == 1
 template <typename T, typename KVT, int D>
@@ -1331,7 +1405,11 @@ static int launch_decode_f(const mi355_attn_params& p, void* ws, size_t ws_bytes
     if (!layout_is_flash(p))   // decode_supported admitted it: the legacy v0 layout
       return feat ? launch_decode_t<T, KVT, D, true, false, true>(p, ws, ws_bytes, stream) : launch_decode_t<T, KVT, D, false, false, true>(p, ws, ws_bytes, stream);
   }
-  if (const int groups = decode_pack_groups(p)) return launch_decode_pack<T, KVT, D>(p, ws, ws_bytes, stream, feat, groups);
+  if (const int groups = decode_pack_groups(p)) {
+    if constexpr (D <= 128)
+      if (groups == 4) return launch_decode_pack4<T, KVT, D>(p, ws, ws_bytes, stream);
+    return launch_decode_pack<T, KVT, D>(p, ws, ws_bytes, stream, feat, groups);
+  }
   if (p.head_size != D)
     return feat ? launch_decode_t<T, KVT, D, true, true, false>(p, ws, ws_bytes, stream) : launch_decode_t<T, KVT, D, false, true, false>(p, ws, ws_bytes, stream);
   return feat ? launch_decode_t<T, KVT, D, true, false, false>(p, ws, ws_bytes, stream) : launch_decode_t<T, KVT, D, false, false, false>(p, ws, ws_bytes, stream);
