@@ -26,9 +26,15 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 800 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 900 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.9.0  No change to the structs or the entry points. Causal prefill calls at head size exactly 256 over a 16-bit cache of
+ *          the query's type, without soft-cap / ALiBi / fused cache write and without a key-split plan, now run on a kernel of
+ *          their own: mi355_last_kernel() answers prefill_mfma_d256, or prefill_mfma_d256_sw with a sliding window (before:
+ *          prefill_mfma / prefill_mfma_feat) - under MI355_SELECT_2D at every length, under MI355_SELECT_AUTO from 512 keys
+ *          (max_seqlen_k) on. fp8 caches, soft-cap, ALiBi, key-split calls, head sizes 160 / 192 / 224 and non_causal keep
+ *          their kernels and names; workspace sizes and mi355_decode_write_fusable() are those of 0.8.0 for every call.
  *   0.8.0  No change to the structs or the entry points. decode_rows_hint now reaches 64 / G: a hint above what two column
  *          groups hold (32 / G) and up to pow2_floor(64 / G) sends rows of up to that many tokens to the decode kernels'
  *          four-column-group form (mi355_last_kernel(): decode_splitkv_pack4[_fp8] / decode_single_pack4[_fp8]) - a step whose

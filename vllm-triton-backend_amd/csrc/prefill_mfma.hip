@@ -1616,6 +1616,20 @@ bool prefill_dma_selected(const mi355_attn_params& p) {
 
 bool prefill_runs_without_key_splits(const mi355_attn_params& p) { return plan_key_splits(p).splits <= 1; }
 
+// launch_prefill (without key splits) hands this call to prefill_d256_kernel (prefill_d256.hip): plain or windowed causal
+// attention at head size 256 over a 16-bit cache, no kernel pinned by MI355_PREFILL (v1 keeps the register-staged kernel: the
+// A/B switch). Under MI355_SELECT_2D at every length; under AUTO from kD256MinKeys keys on: the smallest length measured, and
+// this kernel is ahead at every one (Hq 16 / Hk 8, bf16, graph replay, us per launch, register-staged | this, the former
+// twice within 0.3 %: 1 x 512 28.5 | 25.0, 1 x 1024 47.8 | 41.6, 1 x 2048 without key splits 90.3 | 78.2, 1 x 4096 188.6 | 163.8,
+// 16 x 4096 3158 | 2768, 1 x 16384 2651 | 2331; window 1024: 1 x 4096 112.0 | 93.4, 16 x 4096 1641 | 1344, 1 x 16384 451 | 375;
+// profiles/r08/). Where plan_key_splits() splits (1 x 2048: 76.1 us on two splits) the call stays on the key-split launch.
+constexpr int kD256MinKeys = 512;
+bool prefill_d256_selected(const mi355_attn_params& p) {
+  static const char* const variant = lab_env("MI355_PREFILL");
+  if (variant || !prefill_supported(p) || !prefill_d256_applicable(p) || plan_key_splits(p).splits > 1) return false;
+  return p.kernel_select == MI355_SELECT_2D || p.max_seqlen_k >= kD256MinKeys;
+}
+
 int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks, int* counters) {
   if (!prefill_supported(p)) {
     set_error("prefill kernel does not support this configuration");
@@ -1667,6 +1681,7 @@ int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySpli
   // want the wider ones). MI355_PREFILL=lat pins it wherever it applies.
   if (!ks && prefill_lat_selected(p)) return launch_prefill_lat(p, stream);
   if (p.write_new_kv && (ks || !prefill_dma_selected(p))) { set_error("write_new_kv: this prefill step is not served with a fused cache write (mi355_decode_write_fusable)"); return MI355_ERR_UNSUPPORTED; }
+  if (!ks && prefill_d256_selected(p)) return launch_prefill_d256(p, stream);
   if (!feat && p.head_size == 128 && !v1 && p.kv_dtype == p.q_dtype) {
     // 8 waves / 256-row Q blocks / 3 stages when that still gives every CU two workgroups' worth of Q blocks
     // (it holds one at a time) and the sequences are long enough to amortise a workgroup's un-overlapped
@@ -1690,7 +1705,8 @@ int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySpli
   // (Head size 256 on the LDS-DMA form - prefill_dma_kernel<T, 4, 2, 256>, one workgroup per CU - was built in round 3 and
   // measured 112 TFLOP/s against the register-staged kernel's 494: without staging registers hipcc still moves several
   // hundred values per tile between VGPRs and accumulator registers (432 v_accvgpr_read + 225 v_accvgpr_write per tile
-  // in the ISA, 750 bytes of scratch). Head size 256 needs the hand-owned register file of prefill_pw_kernel.)
+  // in the ISA, 750 bytes of scratch). Head size 256 needs the hand-owned register file of prefill_pw_kernel:
+  // prefill_d256_kernel, prefill_d256.hip, taken above; what reaches the cases below at that size is fp8, features, key splits.)
 #define MI355_PREFILL_CASE(KV, DD)                                                                        \
   case DD:                                                                                                \
     if (feat) return bf ? launch_prefill_t<bf16_t, KV<bf16_t>, DD, true>(p, stream, ks) : launch_prefill_t<f16_t, KV<f16_t>, DD, true>(p, stream, ks); \
