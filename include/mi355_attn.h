@@ -26,9 +26,16 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 900 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 1000 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.10.0 No change to the structs or the entry points. The head-size-256 prefill calls of 0.9.0 now include those over an
+ *          fp8 cache (e4m3 or e5m2, bf16 or f16 queries; every K / V stride a multiple of 16 elements): they run on an fp8 form
+ *          of that kernel and mi355_last_kernel() answers prefill_mfma_fp8_d256, or prefill_mfma_fp8_d256_sw with a sliding
+ *          window (before: prefill_mfma_fp8 / prefill_mfma_fp8_feat) - under MI355_SELECT_2D at every length, under
+ *          MI355_SELECT_AUTO from 512 keys (max_seqlen_k) on. Soft-cap, ALiBi, key-split calls, head sizes 160 / 192 / 224 and
+ *          non_causal keep their kernels and names; workspace sizes and mi355_decode_write_fusable() are those of 0.9.0 for
+ *          every call.
  *   0.9.0  No change to the structs or the entry points. Causal prefill calls at head size exactly 256 over a 16-bit cache of
  *          the query's type, without soft-cap / ALiBi / fused cache write and without a key-split plan, now run on a kernel of
  *          their own: mi355_last_kernel() answers prefill_mfma_d256, or prefill_mfma_d256_sw with a sliding window (before:
@@ -327,9 +334,10 @@ MI355_API size_t mi355_attn_workspace_bytes(const mi355_attn_params* p);
  * Which kernel serves a call (AUTO; mi355_last_kernel() names it afterwards):
  *   matrix-core kernels - f16/bf16 queries, flash-layout cache of the same type or fp8 e4m3fn/e5m2 with scalar
  *     scales, page size a power of two >= 16, head size any multiple of 8 (16 with an fp8 cache) up to 256 (run on
- *     the next of 64/128/256; the reference pads to the next power of two, :353,:912; fp8 prefill up to 128):
+ *     the next of 64/128/256; the reference pads to the next power of two, :353,:912):
  *       max_seqlen_q == 1            -> split-KV decode ("decode_splitkv[_fp8]" / "decode_single[_fp8]")
- *       every sequence a prefill     -> Q-block prefill ("prefill_mfma[_fp8][_feat]"; "..._ksplit" when few Q blocks
+ *       every sequence a prefill     -> Q-block prefill ("prefill_mfma[_fp8][_feat]", "prefill_mfma[_fp8]_d256[_sw]" at head
+ *                                       size 256; "..._ksplit" when few Q blocks
  *                                       face a long context: key tiles dealt to several workgroups, partials merged
  *                                       by lse through the workspace)
  *       mixed batch                  -> both, prefill rows then decode rows ("<prefill kernel>+<decode kernel>", e.g. "prefill_mfma+decode_splitkv")

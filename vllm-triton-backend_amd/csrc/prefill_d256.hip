@@ -35,84 +35,16 @@
 // No fixed reference, so f16 needs no range check and no fix-up launch. Only tiles on the diagonal, the sequence's last
 // partial tile and (SW) the window's edge tiles are masked.
 #include <cstdlib>
-#include <type_traits>
-#include <utility>
 
-#include "common.h"
+#include "prefill_d256.h"
 
 namespace mi355 {
 
-typedef __attribute__((ext_vector_type(4))) unsigned int du32x4_t;
-typedef __attribute__((ext_vector_type(2))) unsigned int du32x2_t;
-typedef __attribute__((ext_vector_type(4))) float df32x4_t;
-typedef __attribute__((ext_vector_type(4))) short ds16x4_t;
-
-constexpr int kDRows = 128;                 // Q-block rows per workgroup
-constexpr int kDTile = 64;                  // keys per tile
 constexpr int kDRowB = 512;                 // bytes per key row (256 x 2)
 constexpr int kDTileB = kDTile * kDRowB;    // 32 KiB: one K or V tile
 constexpr int kDStageB = 2 * kDTileB;       // K tile then V tile
 constexpr int kDLds = 2 * kDStageB;         // two stages
-constexpr int kDAccO = 0, kDAccQ = 128;     // accumulator-register map
-constexpr int kDORS = kDRowB + 16;          // padded row stride of the output rows parked in LDS (epilogue)
-constexpr float kDLog2e = 1.4426950408889634f;
-constexpr float kDDefer = 8.0f;             // log2 units a tile's maximum may exceed the row's reference by before it moves
 static_assert(4 * 32 * kDORS <= kDLds && kDLds <= 160 * 1024, "prefill_d256_kernel: LDS map");
-
-struct D256Args {
-  mi355_attn_params p;
-  int group;        // G
-  int block_q;      // tokens per Q block = 128 / G
-  int page_shift;   // log2(page_size)
-  uint32_t k_page_b, k_slot_b, v_page_b, v_slot_b;   // bytes between pages / key rows; validated < 2^32 on the host
-};
-
-template <typename F, int... I>
-__device__ __forceinline__ void d_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
-template <int N, typename F>
-__device__ __forceinline__ void d_for(F&& f) { d_for_impl(static_cast<F&&>(f), std::make_integer_sequence<int, N>{}); }
-
-// The matrix instructions. asm volatile: they stay in source order, and the compiler neither pads nor counts anything
-// around them - the wait states between them and ordinary code are written out where they are needed.
-template <typename T> struct d256_ops;
-#define MI355_DEF_D256_OPS(TAG, MFMA, CVT)                                                                          \
-  template <> struct d256_ops<TAG> {                                                                               \
-    /* S(VGPR) = K(VGPR) . Q'(AGPR) */                                                                              \
-    template <int QA> static __device__ __forceinline__ void qk_zero(df32x4_t& s, const du32x4_t& k) {             \
-      asm volatile(MFMA " %0, %1, a[%c2:%c3], 0" : "=&v"(s) : "v"(k), "n"(QA), "n"(QA + 3));                        \
-    }                                                                                                              \
-    /* S(VGPR) += K(VGPR) . Q'(AGPR) */                                                                             \
-    template <int QA> static __device__ __forceinline__ void qk_acc(df32x4_t& s, const du32x4_t& k) {              \
-      asm volatile(MFMA " %0, %1, a[%c2:%c3], %0" : "+v"(s) : "v"(k), "n"(QA), "n"(QA + 3));                        \
-    }                                                                                                              \
-    /* O(AGPR) += V(VGPR) . P(VGPR) */                                                                              \
-    template <int OA> static __device__ __forceinline__ void pv(const du32x4_t& v, const du32x4_t& pf) {           \
-      asm volatile(MFMA " a[%c2:%c3], %0, %1, a[%c2:%c3]" :: "v"(v), "v"(pf), "n"(OA), "n"(OA + 3));                \
-    }                                                                                                              \
-    static __device__ __forceinline__ uint32_t pack2(float lo, float hi) {                                         \
-      uint32_t r; asm volatile(CVT " %0, %1, %2" : "=v"(r) : "v"(lo), "v"(hi)); return r;                           \
-    }                                                                                                              \
-  };
-MI355_DEF_D256_OPS(bf16_t, "v_mfma_f32_16x16x32_bf16", "v_cvt_pk_bf16_f32")
-MI355_DEF_D256_OPS(f16_t, "v_mfma_f32_16x16x32_f16", "v_cvt_pk_f16_f32")
-#undef MI355_DEF_D256_OPS
-
-template <int IDX> __device__ __forceinline__ void d_acc_write(uint32_t v) { asm volatile("v_accvgpr_write_b32 a%c0, %1" :: "n"(IDX), "v"(v)); }
-template <int IDX> __device__ __forceinline__ float d_acc_read() { float r; asm volatile("v_accvgpr_read_b32 %0, a%c1" : "=v"(r) : "n"(IDX)); return r; }
-// 2^x, pinned where it stands in the source (the wait state: a transcendental's result and the VALU instruction that reads it)
-__device__ __forceinline__ float d_exp2(float x) { float r; asm volatile("v_exp_f32 %0, %1\n\ts_nop 0" : "=v"(r) : "v"(x)); return r; }
-
-// One block-table entry through the scalar cache, in two halves: the load is started here and landed by d_sload_land(),
-// which the caller places before the first use of `r` - and in the same loop iteration, so that no copy of `r` is made
-// while it is in flight. `base` and `off` (bytes) are wave-uniform.
-__device__ __forceinline__ void d_sload_start(int& r, const int32_t* base, int off) {
-  const uint64_t b = (uint64_t)base;
-  const uint32_t blo = __builtin_amdgcn_readfirstlane((uint32_t)b), bhi = __builtin_amdgcn_readfirstlane((uint32_t)(b >> 32));
-  const uint64_t bu = ((uint64_t)bhi << 32) | blo;
-  const int o = __builtin_amdgcn_readfirstlane(off);
-  asm volatile("s_load_dword %0, %1, %2" : "=&s"(r) : "s"(bu), "s"(o) : "memory");
-}
-__device__ __forceinline__ void d_sload_land(int& r) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(r) :: "memory"); }
 
 template <typename T, bool SW>
 __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) {
@@ -419,13 +351,19 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) 
 // ---------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------
-// Beyond prefill_supported(): exactly head size 256, a 16-bit cache of the query's type, causal, no soft-cap / ALiBi, no
-// fused cache write, output rows the 16-byte stores can address.
+// Beyond prefill_supported(): exactly head size 256, a 16-bit cache of the query's type or an fp8 cache (library 0.10.0:
+// prefill_d256_fp8.hip), causal, no soft-cap / ALiBi, no fused cache write, output rows the 16-byte stores can address.
 bool prefill_d256_applicable(const mi355_attn_params& p) {
-  if (p.head_size != 256 || p.kv_dtype != p.q_dtype) return false;
+  const bool fp8 = p.kv_dtype == MI355_FP8_E4M3 || p.kv_dtype == MI355_FP8_E5M2;
+  if (p.head_size != 256 || (p.kv_dtype != p.q_dtype && !fp8)) return false;
   if (p.softcap > 0.0f || p.alibi_slopes || p.non_causal || p.write_new_kv || p.k_new || p.v_new) return false;
   if (((uintptr_t)p.out & 15) != 0 || p.out_stride_token % 8 != 0 || p.out_stride_head % 8 != 0) return false;
-  if (p.k_stride_page * 2 >= (1LL << 32) || p.v_stride_page * 2 >= (1LL << 32)) return false;     // byte strides in 32 bits
+  const int64_t eb = fp8 ? 1 : 2;                                                                  // bytes per cache element
+  if (p.k_stride_page * eb >= (1LL << 32) || p.v_stride_page * eb >= (1LL << 32)) return false;    // byte strides in 32 bits
+  if (fp8) {                                                                                       // 16-byte LDS-DMA pieces of fp8 rows
+    const int64_t strides[] = {p.k_stride_page, p.k_stride_slot, p.k_stride_head, p.v_stride_page, p.v_stride_slot, p.v_stride_head};
+    for (int64_t s : strides) if (s % 16 != 0) return false;
+  }
   return true;
 }
 
@@ -453,6 +391,7 @@ int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream) {
     set_error("prefill_d256_kernel does not support this configuration");
     return MI355_ERR_UNSUPPORTED;
   }
+  if (p.kv_dtype != p.q_dtype) return launch_prefill_d256_fp8(p, stream);
   const bool bf = p.q_dtype == MI355_BF16;
   if (p.sliding_window > 0) return bf ? launch_d256_t<bf16_t, true>(p, stream) : launch_d256_t<f16_t, true>(p, stream);
   return bf ? launch_d256_t<bf16_t, false>(p, stream) : launch_d256_t<f16_t, false>(p, stream);

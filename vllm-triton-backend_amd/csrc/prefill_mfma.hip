@@ -1624,10 +1624,16 @@ bool prefill_runs_without_key_splits(const mi355_attn_params& p) { return plan_k
 // 16 x 4096 3158 | 2768, 1 x 16384 2651 | 2331; window 1024: 1 x 4096 112.0 | 93.4, 16 x 4096 1641 | 1344, 1 x 16384 451 | 375;
 // profiles/r08/). Where plan_key_splits() splits (1 x 2048: 76.1 us on two splits) the call stays on the key-split launch.
 constexpr int kD256MinKeys = 512;
+// The same rule for an fp8 cache (prefill_d256_fp8_kernel, prefill_d256_fp8.hip; library 0.10.0), with a minimum of its own:
+// again the smallest length measured, and that kernel is ahead at every one (Hq 16 / Hk 8, bf16 over e4m3, graph replay, us per
+// launch, register-staged | this, the former twice within 0.3 %: 1 x 512 26.8 | 25.1, 1 x 1024 44.5 | 41.9, 1 x 2048 without key
+// splits 80.3 | 75.7, 1 x 4096 171.0 | 161.0, 16 x 4096 2722 | 2544, 1 x 16384 2404 | 2287; window 1024: 1 x 4096 104.3 | 89.5,
+// 16 x 4096 1528 | 1283, 1 x 16384 413.1 | 353.4; profiles/r09/).
+constexpr int kD256Fp8MinKeys = 512;
 bool prefill_d256_selected(const mi355_attn_params& p) {
   static const char* const variant = lab_env("MI355_PREFILL");
   if (variant || !prefill_supported(p) || !prefill_d256_applicable(p) || plan_key_splits(p).splits > 1) return false;
-  return p.kernel_select == MI355_SELECT_2D || p.max_seqlen_k >= kD256MinKeys;
+  return p.kernel_select == MI355_SELECT_2D || p.max_seqlen_k >= (p.kv_dtype == p.q_dtype ? kD256MinKeys : kD256Fp8MinKeys);
 }
 
 int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks, int* counters) {
