@@ -26,9 +26,14 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 1000 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 1100 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.11.0 No change to the structs or the entry points. q_dtype = MI355_FP8_E4M3 is accepted (before: MI355_ERR_UNSUPPORTED):
+ *          e4m3 queries over an fp8 cache at head size 128, bf16 output, on fp8 matrix instructions - mi355_last_kernel()
+ *          answers prefill_mfma_q8, or prefill_mfma_q8_sw with a sliding window; one launch for every row of the step, no
+ *          workspace (see q_dtype for what is served and refused). Calls with 16-bit or f32 queries keep their dispatch,
+ *          kernel names, workspace sizes and bits.
  *   0.10.0 No change to the structs or the entry points. The head-size-256 prefill calls of 0.9.0 now include those over an
  *          fp8 cache (e4m3 or e5m2, bf16 or f16 queries; every K / V stride a multiple of 16 elements): they run on an fp8 form
  *          of that kernel and mi355_last_kernel() answers prefill_mfma_fp8_d256, or prefill_mfma_fp8_d256_sw with a sliding
@@ -163,6 +168,21 @@ typedef struct mi355_attn_params {
   /* element types */
   int32_t q_dtype;             /* mi355_dtype of q, out, k_new, v_new                            */
   int32_t kv_dtype;            /* mi355_dtype of the caches (== q_dtype, or an fp8 type)         */
+  /* library version >= 0.11.0: q_dtype = MI355_FP8_E4M3 - fp8 queries. q is OCP e4m3fn with a query scale of 1.0 (one byte an
+   * element, strides in bytes) and `out` IS BF16 BY DEFINITION (no field could say otherwise; out strides in bf16 elements).
+   * kv_dtype is MI355_FP8_E4M3 or MI355_FP8_E5M2. The call computes
+   *     S_ij = scale * k_scale * sum_d q_id k_jd   under the causal mask and the optional sliding window,
+   *     out_i = v_scale * sum_j P_ij v_j / sum_j P_ij  (bf16),   lse_i = log sum_j exp(S_ij),   sinks as in 0.7.0
+   * - with both scales 1.0 the fp8-query branch of the reference's kernel (triton_unified_attention.py:434-455,:508). The products
+   * run on fp8 matrix instructions with fp32 accumulation, nothing is widened. P enters the second product in e4m3 as TWO
+   * terms, the weight rounded to e4m3 (the reference's P.to(V.dtype)) and its rounding residual rounded to e4m3, scaled by 2^8
+   * into the upper e4m3 range; the row sum is taken from the same two terms.
+   * Served: head size 128, flash layout, page size a power of two >= 32, every q / K / V stride a multiple of 16 elements,
+   * 16-byte aligned q / out / caches, every query length including 1 (decode rows ride the same launch), skip_decodes /
+   * only_decodes, lse and sinks optional; mi355_attn_workspace_bytes() answers 0. Refused (MI355_ERR_UNSUPPORTED, the message
+   * names the cause, before any HIP call): e5m2 queries, other head sizes, soft-cap, ALiBi, non_causal, k_new / v_new,
+   * write_new_kv (mi355_decode_write_fusable() answers 0), MI355_SELECT_3D / MI355_SELECT_GENERIC, the legacy layout and the
+   * two legacy entry points, a key-split plan (num_segments > 1). */
 
   /* sizes */
   int32_t num_tokens;          /* T  = q.shape[0]                                                */
@@ -350,6 +370,8 @@ MI355_API size_t mi355_attn_workspace_bytes(const mi355_attn_params* p);
  *     kernel covers it ("repack+<prefill kernel>[+<decode kernel>]")
  *     (an fp8 cache is dequantised into the 16-bit scratch: (fp8 -> f32) * scale -> query type; since 0.6.1 a plain fp8
  *     flash-layout prefill at head size 128 does not come this way: "prefill_mfma_pw_fp8" widens the tiles itself)
+ *   fp8 e4m3 queries (library 0.11.0; fp8 cache, head size 128, bf16 output: see q_dtype) -> "prefill_mfma_q8[_sw]", every row
+ *     of the step in one launch, no workspace; nothing else serves them
  *   everything else (f32, head sizes that are not a multiple of 8 or exceed 256, ...) -> "generic".
  */
 MI355_API int mi355_unified_attention(const mi355_attn_params* p, void* workspace, size_t workspace_bytes,

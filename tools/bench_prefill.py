@@ -35,6 +35,7 @@ def main():
     ap.add_argument("--legacy", action="store_true", help="context_attention_fwd: v0 cache layout for the first --ctx keys, the rest from linear k/v")
     ap.add_argument("--ctx", type=int, default=0, help="context keys per sequence already in the cache (query length = seq - ctx)")
     ap.add_argument("--generic", action="store_true", help="with --legacy: force the shape-agnostic kernel (the path before the repack)")
+    ap.add_argument("--q-fp8", action="store_true", help="e4m3 queries over the fp8 cache (prefill_mfma_q8; needs --kvdtype fp8 / fp8_e5m2, --page >= 32; bf16 output)")
     args = ap.parse_args()
     dev = torch.device("cuda:0")
     dt = torch.bfloat16 if args.dtype == "bf16" else torch.float16
@@ -51,6 +52,8 @@ def main():
     cu = (torch.arange(B + 1, dtype=torch.int32, device=dev) * L).to(torch.int32)
     sl = torch.full((B,), L, dtype=torch.int32, device=dev)
     out = torch.empty_like(q)
+    if args.q_fp8:
+        q = q.to(torch.float8_e4m3fn)
     flops = 4 * L * L * args.d * args.hq / 2 * B
     win = (args.window - 1, 0) if args.window else (-1, -1)
     if args.window:          # row at position i sees min(i + 1, window) keys
@@ -63,7 +66,7 @@ def main():
     if args.ctx and not args.legacy:     # chunked prefill through unified_attention: the last seq - ctx tokens are the queries
         QL = L - args.ctx
         q = q[: B * QL].contiguous()
-        out = torch.empty_like(q)
+        out = out[: B * QL].contiguous()
         cu = (torch.arange(B + 1, dtype=torch.int32, device=dev) * QL).to(torch.int32)
         flops = 4 * args.d * args.hq * (QL * args.ctx + QL * (QL + 1) / 2) * B
         p, keep = ua_mod.fill_attn_params(q, k, v, out, cu, QL, sl, L, 1.0 / math.sqrt(args.d), (-1, -1), bt, 0.0, ksc, ksc, None, None)

@@ -34,7 +34,7 @@ static int validate(const mi355_attn_params* p) {
     return MI355_ERR_BAD_ARG;
   }
   if ((p->k_new == nullptr) != (p->v_new == nullptr)) { set_error("k_new and v_new must be given together"); return MI355_ERR_BAD_ARG; }
-  if (!is_q_dtype(p->q_dtype)) { set_error("q dtype %d is not one of f32/f16/bf16", p->q_dtype); return MI355_ERR_UNSUPPORTED; }
+  if (!is_q_dtype(p->q_dtype) && !is_fp8(p->q_dtype)) { set_error("q dtype %d is not one of f32/f16/bf16/fp8 e4m3", p->q_dtype); return MI355_ERR_UNSUPPORTED; }
   if (p->kv_dtype != p->q_dtype && !is_fp8(p->kv_dtype)) {
     set_error("kv dtype %d must equal the q dtype %d or be an fp8 type", p->kv_dtype, p->q_dtype);
     return MI355_ERR_UNSUPPORTED;
@@ -66,6 +66,8 @@ static int validate(const mi355_attn_params* p) {
     set_error("sinks go with neither non_causal attention nor a fused cache write (write_new_kv)");
     return MI355_ERR_UNSUPPORTED;
   }
+  // fp8 queries (library 0.11.0): one kernel family of its own serves them or nobody does (prefill_q8.hip names the cause)
+  if (is_fp8(p->q_dtype) && !prefill_q8_supported(*p)) return MI355_ERR_UNSUPPORTED;
   if (p->slot_mapping && p->slot_mapping_i32) { set_error("at most one of slot_mapping / slot_mapping_i32 may be non-NULL"); return MI355_ERR_BAD_ARG; }
   if (p->new_kv_all_rows && (!p->k_new || p->write_new_kv)) { set_error("new_kv_all_rows needs k_new / v_new and excludes write_new_kv"); return MI355_ERR_BAD_ARG; }
   if (p->write_new_kv) {
@@ -86,10 +88,11 @@ static int validate(const mi355_attn_params* p) {
 // AUTO policy. The reference picks 3D iff max_seqlen_q == 1 (:884). We do the same for the
 // split-KV decode kernel, send everything else the MFMA prefill kernel covers there, and the
 // remainder to the generic kernel.
-enum class Path { Generic, Decode, Prefill, PrefillPlusDecode, Repacked };
+enum class Path { Generic, Decode, Prefill, PrefillPlusDecode, Repacked, PrefillQ8 };
 
 static Path choose(const mi355_attn_params& p) {
   const int sel = p.kernel_select;
+  if (is_fp8(p.q_dtype)) return Path::PrefillQ8;      // validated: every row of the step, decode rows included, in one launch without a workspace
   if (p.write_new_kv) {      // validated: the fused decode kernel / the prefill kernels that carry the write take it
     if (p.max_seqlen_q == 1 && p.num_tokens == p.num_seqs) return Path::Decode;
     return (p.num_seqs == 1 || (int64_t)p.num_seqs * p.max_seqlen_q == p.num_tokens) ? Path::Prefill : Path::PrefillPlusDecode;
@@ -145,6 +148,8 @@ static int dispatch_plain(const mi355_attn_params& p, void* workspace, size_t wo
       return launch_decode(p, workspace, workspace_bytes, s);
     case Path::Prefill:
       return launch_prefill_ws(p, workspace, workspace_bytes, s);
+    case Path::PrefillQ8:
+      return launch_prefill_q8(p, s);
     case Path::PrefillPlusDecode: {
       mi355_attn_params pp = p, pd = p;
       pp.skip_decodes = pd.only_decodes = p.write_new_kv ? 1 : decode_rows_max_q(p);    // (1, or what one packed decode unit holds: multi-token decode rows; a fused cache write: one-token rows only)
@@ -243,6 +248,7 @@ int mi355_unified_attention(const mi355_attn_params* p, void* workspace, size_t 
 int mi355_decode_write_fusable(const mi355_attn_params* p) {
   if (!p || p->num_tokens <= 0 || p->num_seqs <= 0) return 0;
   if (p->sinks) return 0;                        // (validate() refuses the pair)
+  if (is_fp8(p->q_dtype)) return 0;              // (fp8 queries carry no fused cache write)
   if (p->max_seqlen_q == 1 && p->num_tokens == p->num_seqs) return decode_write_fusable(*p) ? 1 : 0;
   return prefill_write_fusable(*p) ? 1 : 0;      // (library 0.6.0: a prefill step in one launch of the short-prompt kernel)
 }
@@ -252,6 +258,7 @@ int mi355_context_attention_fwd_v0(const mi355_attn_params* p, void* workspace, 
   if (!p->k_new || !p->v_new) { set_error("context_attention_fwd needs the linear k_new / v_new of the tokens being prefilled"); return MI355_ERR_BAD_ARG; }
   if (p->only_decodes) { set_error("context_attention_fwd never computes query_len == 1 rows (only_decodes must be 0)"); return MI355_ERR_BAD_ARG; }
   if (p->sinks) { set_error("context_attention_fwd has no attention sinks (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
+  if (is_fp8(p->q_dtype)) { set_error("context_attention_fwd takes no fp8 queries (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
   mi355_attn_params q = *p;
   q.skip_decodes = 1;                          // rows of query_len == 1 sequences stay untouched (triton_prefix_prefill.py:83-84)
   return mi355_unified_attention(&q, workspace, workspace_bytes, stream);
@@ -261,6 +268,7 @@ int mi355_paged_attention_v0(const mi355_attn_params* p, void* workspace, size_t
   if (!p) { set_error("params is NULL"); return MI355_ERR_BAD_ARG; }
   if (p->k_new || p->v_new) { set_error("paged_attention reads every key from the cache (k_new / v_new must be NULL)"); return MI355_ERR_BAD_ARG; }
   if (p->sinks) { set_error("paged_attention has no attention sinks (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
+  if (is_fp8(p->q_dtype)) { set_error("paged_attention takes no fp8 queries (mi355_unified_attention takes them)"); return MI355_ERR_UNSUPPORTED; }
   if (p->max_seqlen_q != 1 || p->num_tokens != p->num_seqs) {
     set_error("paged_attention is a decode op: one query token per sequence (max_seqlen_q %d, num_tokens %d, num_seqs %d)", p->max_seqlen_q, p->num_tokens, p->num_seqs);
     return MI355_ERR_BAD_ARG;

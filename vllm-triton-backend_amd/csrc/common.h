@@ -491,6 +491,8 @@ bool prefill_runs_without_key_splits(const mi355_attn_params& p);
 bool prefill_d256_applicable(const mi355_attn_params& p);  // head size 256 kernel, prefill_d256.hip: beyond prefill_supported()
 int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream);
 bool prefill_d256_selected(const mi355_attn_params& p);    // launch_prefill (no key splits) hands this call to prefill_d256_kernel
+bool prefill_q8_supported(const mi355_attn_params& p);     // fp8 queries (prefill_q8.hip, library 0.11.0): what such a call must be; sets the error message otherwise
+int launch_prefill_q8(const mi355_attn_params& p, hipStream_t stream);
 bool prefill_write_fusable(const mi355_attn_params& p);    // a prefill step whose cache write can ride the attention launch (write_new_kv)
 
 inline int check_hip(hipError_t e, const char* what) {

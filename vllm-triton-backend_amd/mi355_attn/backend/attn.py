@@ -33,6 +33,9 @@ _FUSED_PREFILL_WRITE = os.environ.get("MI355_FUSED_PREFILL_WRITE", "1") != "0"  
 # the same over an fp8 cache (library 0.6.2): OFF by default - measured slower than the pair of calls (23.1 against 17.3 us per layer
 # at 1 x 512, profiles/r05/fused_prefill_write_fp8.log); =1 takes the fused path where the library answers for the step
 _FUSED_PREFILL_WRITE_FP8 = os.environ.get("MI355_FUSED_PREFILL_WRITE_FP8", "0") == "1"
+# fp8 queries over an fp8 cache (library 0.11.0, prefill_mfma_q8): OFF by default; =1 quantises the query (clamp to +-448, cast
+# to e4m3, query scale 1.0 - what the reference's backend does off ROCm, triton_attn.py:407-421) for steps with prefill rows
+_FP8_QUERY = os.environ.get("MI355_FP8_QUERY", "0") == "1"
 _lib.load()  # fail at import, not at the first forward, if the HIP library is missing
 
 
@@ -371,6 +374,12 @@ class MI355AttentionImpl(AttentionImpl):
             out = out.view(-1, self.num_heads, self.head_size)
         if q.dim() == 2:
             q = q.view(-1, self.num_heads, self.head_size)
+
+        # MI355_FP8_QUERY=1: a step with prefill rows over an fp8 cache runs on fp8 matrix instructions end to end (decode-only
+        # steps keep 16-bit queries and the split-KV kernel). _q_scale_checked: the layer's query scale is known to be 1.0.
+        if (_FP8_QUERY and fp8 and self._q_scale_checked and self.head_size == 128 and not self.logits_soft_cap and self.alibi_slopes is None
+                and out.dtype == torch.bfloat16 and int(max_seqlen_q) > 1 and key_cache.shape[1] >= 32):
+            q = q.clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
 
         # (avg_seqlen_q/k only fed the reference's autotuner keys, triton_unified_attention.py:878-881: not passed on)
         torch.ops.mi355_attn.unified_attention(

@@ -44,6 +44,9 @@ def fill_attn_params(
         raise ValueError("q and out must be [num_tokens, num_heads, head_size]")
     if q.stride(2) != 1 or out.stride(2) != 1:
         raise ValueError("last dimension of q and out must be contiguous")
+    if q.element_size() == 1 and out.dtype != torch.bfloat16:
+        # the struct has one dtype field for q and out: with fp8 queries the output is bf16 by definition (include/mi355_attn.h, q_dtype)
+        raise ValueError("with fp8 queries `out` must be a torch.bfloat16 tensor")
     if cu_seqlens_q.dtype != torch.int32 or seqused_k.dtype != torch.int32 or block_table.dtype != torch.int32:
         raise ValueError("cu_seqlens_q, seqused_k and block_table must be int32")
     if not (cu_seqlens_q.is_contiguous() and seqused_k.is_contiguous()):
