@@ -26,9 +26,16 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 1100 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 1200 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.12.0 No change to the structs or the entry points. A pure decode step with fp8 queries (max_seqlen_q == 1, num_tokens ==
+ *          num_seqs, no skip_decodes / only_decodes) under MI355_SELECT_AUTO with at most 16 query heads per KV head runs on a
+ *          split-KV kernel family of its own: mi355_last_kernel() answers decode_splitkv_q8, or decode_single_q8 for a one-split
+ *          plan. For such a step mi355_attn_workspace_bytes() is no longer always 0 (the counter region plus the split partials
+ *          when the plan has several splits), and num_segments = N > 0 is accepted as its split count. A 0.11.0 caller that
+ *          passes no workspace keeps working: without the workspace the step runs on prefill_mfma_q8 as before. Every other
+ *          call - MI355_SELECT_2D, mixed steps, more than 16 query heads per KV head - keeps its kernel, name, workspace and bits.
  *   0.11.0 No change to the structs or the entry points. q_dtype = MI355_FP8_E4M3 is accepted (before: MI355_ERR_UNSUPPORTED):
  *          e4m3 queries over an fp8 cache at head size 128, bf16 output, on fp8 matrix instructions - mi355_last_kernel()
  *          answers prefill_mfma_q8, or prefill_mfma_q8_sw with a sliding window; one launch for every row of the step, no
@@ -179,10 +186,16 @@ typedef struct mi355_attn_params {
    * into the upper e4m3 range; the row sum is taken from the same two terms.
    * Served: head size 128, flash layout, page size a power of two >= 32, every q / K / V stride a multiple of 16 elements,
    * 16-byte aligned q / out / caches, every query length including 1 (decode rows ride the same launch), skip_decodes /
-   * only_decodes, lse and sinks optional; mi355_attn_workspace_bytes() answers 0. Refused (MI355_ERR_UNSUPPORTED, the message
-   * names the cause, before any HIP call): e5m2 queries, other head sizes, soft-cap, ALiBi, non_causal, k_new / v_new,
-   * write_new_kv (mi355_decode_write_fusable() answers 0), MI355_SELECT_3D / MI355_SELECT_GENERIC, the legacy layout and the
-   * two legacy entry points, a key-split plan (num_segments > 1). */
+   * only_decodes, lse and sinks optional. mi355_attn_workspace_bytes() answers 0, except - library 0.12.0 - for a pure decode
+   * step under MI355_SELECT_AUTO with at most 16 query heads per KV head whose plan has several splits (num_segments = N > 0
+   * names the count as an upper bound - splits are whole 128-key tiles: with T = ceil(max_seqlen_k / 128) and n = min(N, T, 128)
+   * the plan has ceil(T / ceil(T / n)) splits, one when max_seqlen_k is 0 (no bound given) or at most 128 - and 0 lets the
+   * library plan it from num_seqs, num_kv_heads and max_seqlen_k; ask
+   * mi355_attn_workspace_bytes() for the size, never derive it from N): the counter region plus
+   * num_seqs * Hq * splits partials of 128 + 32 floats; called without that workspace the step runs as in 0.11.0. Refused
+   * (MI355_ERR_UNSUPPORTED, the message names the cause, before any HIP call): e5m2 queries, other head sizes, soft-cap, ALiBi,
+   * non_causal, k_new / v_new, write_new_kv (mi355_decode_write_fusable() answers 0), MI355_SELECT_3D / MI355_SELECT_GENERIC,
+   * the legacy layout and the two legacy entry points, a key-split plan (num_segments > 1) on anything but such a decode step. */
 
   /* sizes */
   int32_t num_tokens;          /* T  = q.shape[0]                                                */
@@ -371,7 +384,9 @@ MI355_API size_t mi355_attn_workspace_bytes(const mi355_attn_params* p);
  *     (an fp8 cache is dequantised into the 16-bit scratch: (fp8 -> f32) * scale -> query type; since 0.6.1 a plain fp8
  *     flash-layout prefill at head size 128 does not come this way: "prefill_mfma_pw_fp8" widens the tiles itself)
  *   fp8 e4m3 queries (library 0.11.0; fp8 cache, head size 128, bf16 output: see q_dtype) -> "prefill_mfma_q8[_sw]", every row
- *     of the step in one launch, no workspace; nothing else serves them
+ *     of the step in one launch, no workspace; a pure decode step under MI355_SELECT_AUTO with at most 16 query heads per KV
+ *     head (library 0.12.0) -> "decode_splitkv_q8" + merge launch, "decode_single_q8" for a one-split plan, and
+ *     "prefill_mfma_q8" when the call brings no workspace; nothing else serves them
  *   everything else (f32, head sizes that are not a multiple of 8 or exceed 256, ...) -> "generic".
  */
 MI355_API int mi355_unified_attention(const mi355_attn_params* p, void* workspace, size_t workspace_bytes,

@@ -67,7 +67,12 @@ static int validate(const mi355_attn_params* p) {
     return MI355_ERR_UNSUPPORTED;
   }
   // fp8 queries (library 0.11.0): one kernel family of its own serves them or nobody does (prefill_q8.hip names the cause)
-  if (is_fp8(p->q_dtype) && !prefill_q8_supported(*p)) return MI355_ERR_UNSUPPORTED;
+  // (library 0.12.0: a decode step the split-KV family takes may name its split count - num_segments is refused everywhere else)
+  if (is_fp8(p->q_dtype)) {
+    mi355_attn_params c = *p;
+    if (decode_q8_step(c) && c.num_segments > 0) c.num_segments = 0;
+    if (!prefill_q8_supported(c)) return MI355_ERR_UNSUPPORTED;
+  }
   if (p->slot_mapping && p->slot_mapping_i32) { set_error("at most one of slot_mapping / slot_mapping_i32 may be non-NULL"); return MI355_ERR_BAD_ARG; }
   if (p->new_kv_all_rows && (!p->k_new || p->write_new_kv)) { set_error("new_kv_all_rows needs k_new / v_new and excludes write_new_kv"); return MI355_ERR_BAD_ARG; }
   if (p->write_new_kv) {
@@ -88,11 +93,13 @@ static int validate(const mi355_attn_params* p) {
 // AUTO policy. The reference picks 3D iff max_seqlen_q == 1 (:884). We do the same for the
 // split-KV decode kernel, send everything else the MFMA prefill kernel covers there, and the
 // remainder to the generic kernel.
-enum class Path { Generic, Decode, Prefill, PrefillPlusDecode, Repacked, PrefillQ8 };
+enum class Path { Generic, Decode, Prefill, PrefillPlusDecode, Repacked, PrefillQ8, DecodeQ8 };
 
 static Path choose(const mi355_attn_params& p) {
   const int sel = p.kernel_select;
-  if (is_fp8(p.q_dtype)) return Path::PrefillQ8;      // validated: every row of the step, decode rows included, in one launch without a workspace
+  // validated fp8 queries: a pure decode step on the split-KV family (library 0.12.0); anything else - every row of the step,
+  // decode rows included - in one launch of the Q-block kernel without a workspace
+  if (is_fp8(p.q_dtype)) return decode_q8_step(p) ? Path::DecodeQ8 : Path::PrefillQ8;
   if (p.write_new_kv) {      // validated: the fused decode kernel / the prefill kernels that carry the write take it
     if (p.max_seqlen_q == 1 && p.num_tokens == p.num_seqs) return Path::Decode;
     return (p.num_seqs == 1 || (int64_t)p.num_seqs * p.max_seqlen_q == p.num_tokens) ? Path::Prefill : Path::PrefillPlusDecode;
@@ -131,6 +138,7 @@ static size_t plain_workspace_bytes(const mi355_attn_params& p) {
   switch (choose(p)) {
     case Path::Decode: return decode_workspace_bytes(p);
     case Path::Prefill: return prefill_workspace_bytes(p);
+    case Path::DecodeQ8: return decode_q8_workspace_bytes(p);
     case Path::PrefillPlusDecode: {          // the two run one after the other on the stream and share the bytes
       mi355_attn_params pp = p, pd = p;
       pp.skip_decodes = pd.only_decodes = p.write_new_kv ? 1 : decode_rows_max_q(p);
@@ -150,6 +158,8 @@ static int dispatch_plain(const mi355_attn_params& p, void* workspace, size_t wo
       return launch_prefill_ws(p, workspace, workspace_bytes, s);
     case Path::PrefillQ8:
       return launch_prefill_q8(p, s);
+    case Path::DecodeQ8:
+      return launch_decode_q8(p, workspace, workspace_bytes, s);
     case Path::PrefillPlusDecode: {
       mi355_attn_params pp = p, pd = p;
       pp.skip_decodes = pd.only_decodes = p.write_new_kv ? 1 : decode_rows_max_q(p);    // (1, or what one packed decode unit holds: multi-token decode rows; a fused cache write: one-token rows only)

@@ -493,6 +493,9 @@ int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream);
 bool prefill_d256_selected(const mi355_attn_params& p);    // launch_prefill (no key splits) hands this call to prefill_d256_kernel
 bool prefill_q8_supported(const mi355_attn_params& p);     // fp8 queries (prefill_q8.hip, library 0.11.0): what such a call must be; sets the error message otherwise
 int launch_prefill_q8(const mi355_attn_params& p, hipStream_t stream);
+bool decode_q8_step(const mi355_attn_params& p);           // fp8 queries (decode_q8.hip, library 0.12.0): a pure decode step under AUTO with G <= 16 - the split-KV family takes it
+size_t decode_q8_workspace_bytes(const mi355_attn_params& p);   // 0 for a one-split plan
+int launch_decode_q8(const mi355_attn_params& p, void* ws, size_t ws_bytes, hipStream_t stream);   // (no or too small a workspace: launch_prefill_q8)
 bool prefill_write_fusable(const mi355_attn_params& p);    // a prefill step whose cache write can ride the attention launch (write_new_kv)
 
 inline int check_hip(hipError_t e, const char* what) {

@@ -34,7 +34,8 @@ _FUSED_PREFILL_WRITE = os.environ.get("MI355_FUSED_PREFILL_WRITE", "1") != "0"  
 # at 1 x 512, profiles/r05/fused_prefill_write_fp8.log); =1 takes the fused path where the library answers for the step
 _FUSED_PREFILL_WRITE_FP8 = os.environ.get("MI355_FUSED_PREFILL_WRITE_FP8", "0") == "1"
 # fp8 queries over an fp8 cache (library 0.11.0, prefill_mfma_q8): OFF by default; =1 quantises the query (clamp to +-448, cast
-# to e4m3, query scale 1.0 - what the reference's backend does off ROCm, triton_attn.py:407-421) for steps with prefill rows
+# to e4m3, query scale 1.0 - what the reference's backend does off ROCm, triton_attn.py:407-421) for steps with prefill rows and - library 0.12.0, decode_splitkv_q8 - for decode-only steps of models with at
+# most 16 query heads per KV head (measured slower there than 16-bit queries on decode_splitkv_fp8: profiles/r11/README.md)
 _FP8_QUERY = os.environ.get("MI355_FP8_QUERY", "0") == "1"
 _lib.load()  # fail at import, not at the first forward, if the HIP library is missing
 
@@ -277,6 +278,17 @@ class MI355AttentionImpl(AttentionImpl):
         assert qs == 1.0, "A non 1.0 q_scale is not currently supported."
         self._q_scale_checked = True
 
+    def _quantises_query(self, layer, max_seqlen_q: int, out_dtype: torch.dtype, page_size: int) -> bool:
+        """MI355_FP8_QUERY=1: does a step of this many query tokens per sequence run with its query cast to e4m3? The ONE
+        predicate behind both decisions in forward() - giving up the fused decode launch and the cast itself. Steps with
+        prefill rows run on prefill_mfma_q8, decode-only steps (library 0.12.0) on decode_splitkv_q8 when a KV head has at most
+        16 query heads (more: they keep 16-bit queries and the split-KV kernel). The layer's query scale must be KNOWN to be 1.0."""
+        if not (_FP8_QUERY and self.kv_cache_dtype.startswith("fp8")):
+            return False
+        self._check_q_scale(layer)
+        return (self._q_scale_checked and self.head_size == 128 and not self.logits_soft_cap and self.alibi_slopes is None
+                and out_dtype == torch.bfloat16 and (int(max_seqlen_q) > 1 or self.num_queries_per_kv <= 16) and page_size >= 32)
+
     def forward(
         self,
         layer: torch.nn.Module,
@@ -306,7 +318,10 @@ class MI355AttentionImpl(AttentionImpl):
         # vLLM's slot_mapping of such a step points at position seq_len - 1 of each sequence, which is where the kernel writes.
         # (a layer with sinks always takes the two calls at the end: the fused cache writes carry no sinks)
         plain = self.alibi_slopes is None and self.sliding_window == (-1, -1) and not self.logits_soft_cap and self.sinks is None
-        if (attn_metadata.max_query_len == 1 and plain and self.kv_sharing_target_layer_name is None
+        # MI355_FP8_QUERY=1 (library 0.12.0): a decode-only step that quantises its query, below, runs on the fp8-query split-KV
+        # kernel - the fused launch here takes 16-bit queries only
+        fp8q_decode = attn_metadata.max_query_len == 1 and self._quantises_query(layer, 1, output.dtype, key_cache.shape[1])
+        if (attn_metadata.max_query_len == 1 and plain and self.kv_sharing_target_layer_name is None and not fp8q_decode
                 and not (self.use_irope and attn_metadata.local_attn_metadata is not None) and _FUSED_DECODE_WRITE):
             q = query[:num_actual_tokens]
             out = output[:num_actual_tokens]
@@ -375,10 +390,8 @@ class MI355AttentionImpl(AttentionImpl):
         if q.dim() == 2:
             q = q.view(-1, self.num_heads, self.head_size)
 
-        # MI355_FP8_QUERY=1: a step with prefill rows over an fp8 cache runs on fp8 matrix instructions end to end (decode-only
-        # steps keep 16-bit queries and the split-KV kernel). _q_scale_checked: the layer's query scale is known to be 1.0.
-        if (_FP8_QUERY and fp8 and self._q_scale_checked and self.head_size == 128 and not self.logits_soft_cap and self.alibi_slopes is None
-                and out.dtype == torch.bfloat16 and int(max_seqlen_q) > 1 and key_cache.shape[1] >= 32):
+        # MI355_FP8_QUERY=1: a step over an fp8 cache runs on fp8 matrix instructions end to end (_quantises_query)
+        if self._quantises_query(layer, max_seqlen_q, out.dtype, key_cache.shape[1]):
             q = q.clamp(-448.0, 448.0).to(torch.float8_e4m3fn)
 
         # (avg_seqlen_q/k only fed the reference's autotuner keys, triton_unified_attention.py:878-881: not passed on)
