@@ -26,9 +26,18 @@
 extern "C" {
 #endif
 
-#define MI355_ATTN_VERSION 1200 /* major*10000 + minor*100 + patch */
+#define MI355_ATTN_VERSION 1300 /* major*10000 + minor*100 + patch */
 /*
  * Version notes (what a caller written against an older header must know)
+ *   0.13.0 No change to the structs or the entry points. The head-size-256 prefill calls of 0.9.0 / 0.10.0 now include those
+ *          with a key-split plan (fewer than 512 Q-block workgroups over at least 32 key tiles - a chunk of a long prompt - or
+ *          num_segments = N > 1), and the prefill half of a mixed step built on one: they run on a key-split form of those
+ *          kernels and mi355_last_kernel() answers prefill_mfma_d256_ksplit, prefill_mfma_d256_sw_ksplit,
+ *          prefill_mfma_fp8_d256_ksplit or prefill_mfma_fp8_d256_sw_ksplit (before: prefill_mfma_ksplit,
+ *          prefill_mfma_feat_ksplit, prefill_mfma_fp8_ksplit, prefill_mfma_fp8_feat_ksplit) - under MI355_SELECT_2D at every
+ *          length, under MI355_SELECT_AUTO from 512 keys (max_seqlen_k) on. The split plan, and with it
+ *          mi355_attn_workspace_bytes() and the workspace layout, are those of 0.12.0 for every call. Soft-cap, ALiBi,
+ *          non_causal, write_new_kv, k_new / v_new and head sizes 160 / 192 / 224 keep their kernels and names.
  *   0.12.0 No change to the structs or the entry points. A pure decode step with fp8 queries (max_seqlen_q == 1, num_tokens ==
  *          num_seqs, no skip_decodes / only_decodes) under MI355_SELECT_AUTO with at most 16 query heads per KV head runs on a
  *          split-KV kernel family of its own: mi355_last_kernel() answers decode_splitkv_q8, or decode_single_q8 for a one-split
@@ -372,7 +381,8 @@ MI355_API size_t mi355_attn_workspace_bytes(const mi355_attn_params* p);
  *       every sequence a prefill     -> Q-block prefill ("prefill_mfma[_fp8][_feat]", "prefill_mfma[_fp8]_d256[_sw]" at head
  *                                       size 256; "..._ksplit" when few Q blocks
  *                                       face a long context: key tiles dealt to several workgroups, partials merged
- *                                       by lse through the workspace)
+ *                                       by lse through the workspace - since 0.13.0 the head-size-256 kernels too:
+ *                                       "prefill_mfma[_fp8]_d256[_sw]_ksplit")
  *       mixed batch                  -> both, prefill rows then decode rows ("<prefill kernel>+<decode kernel>", e.g. "prefill_mfma+decode_splitkv")
  *     the legacy v0 layout (16-bit, k_x == 8, head size 64/128/256) with max_seqlen_q == 1 -> the same split-KV decode
  *     kernel reading that layout directly ("decode_splitkv_v0" / "decode_single_v0")

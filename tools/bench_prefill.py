@@ -69,7 +69,10 @@ def main():
         out = out[: B * QL].contiguous()
         cu = (torch.arange(B + 1, dtype=torch.int32, device=dev) * QL).to(torch.int32)
         flops = 4 * args.d * args.hq * (QL * args.ctx + QL * (QL + 1) / 2) * B
-        p, keep = ua_mod.fill_attn_params(q, k, v, out, cu, QL, sl, L, 1.0 / math.sqrt(args.d), (-1, -1), bt, 0.0, ksc, ksc, None, None)
+        if args.window:      # chunk row i sits at position ctx + i
+            flops = 4 * args.d * args.hq * sum(min(args.ctx + i + 1, args.window) for i in range(QL)) * B
+        p, keep = ua_mod.fill_attn_params(q, k, v, out, cu, QL, sl, L, 1.0 / math.sqrt(args.d), win, bt, 0.0, ksc, ksc, None, None,
+                                          num_segments=args.segments)
     if args.legacy:
         QL = L - args.ctx
         q = q[: B * QL].contiguous()

@@ -489,8 +489,8 @@ bool prefill_lat_selected(const mi355_attn_params& p);     // launch_prefill han
 bool prefill_dma_selected(const mi355_attn_params& p);     // launch_prefill (no key splits) hands this call to an LDS-DMA kernel
 bool prefill_runs_without_key_splits(const mi355_attn_params& p);
 bool prefill_d256_applicable(const mi355_attn_params& p);  // head size 256 kernel, prefill_d256.hip: beyond prefill_supported()
-int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream);
-bool prefill_d256_selected(const mi355_attn_params& p);    // launch_prefill (no key splits) hands this call to prefill_d256_kernel
+int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks = nullptr);   // ks: its key-split form
+bool prefill_d256_selected(const mi355_attn_params& p, const KeySplitCtx* ks = nullptr);    // launch_prefill hands this call to prefill_d256_kernel (ks: to its key-split form)
 bool prefill_q8_supported(const mi355_attn_params& p);     // fp8 queries (prefill_q8.hip, library 0.11.0): what such a call must be; sets the error message otherwise
 int launch_prefill_q8(const mi355_attn_params& p, hipStream_t stream);
 bool decode_q8_step(const mi355_attn_params& p);           // fp8 queries (decode_q8.hip, library 0.12.0): a pure decode step under AUTO with G <= 16 - the split-KV family takes it

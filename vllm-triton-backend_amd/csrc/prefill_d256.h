@@ -26,7 +26,19 @@ struct D256Args {
   int block_q;      // tokens per Q block = 128 / G
   int page_shift;   // log2(page_size)
   uint32_t k_page_b, k_slot_b, v_page_b, v_slot_b;   // bytes between pages / key rows; validated < 2^32 on the host
+  // key-split instantiations only (KS; grid.y = key_splits): workgroup (x, s) walks the s-th even share of its Q block's own
+  // tile range and writes normalised partial rows / lse to p.out + s * out_split_stride / p.lse + s * lse_split_stride
+  int key_splits;
+  int64_t out_split_stride, lse_split_stride;        // elements
 };
+
+// The share of split `s` of a Q block's tile range [lo, hi) (prefill_mfma_kernel's rule: the host knows only the longest
+// sequence, so every Q block deals its OWN tiles). Empty - lo == hi - where the range has fewer tiles than splits.
+__device__ __forceinline__ void d_key_share(int& lo, int& hi, int s, int splits) {
+  const int tps = (max(hi - lo, 0) + splits - 1) / splits;
+  lo = min(lo + s * tps, hi);
+  hi = min(hi, lo + tps);
+}
 
 template <typename F, int... I>
 __device__ __forceinline__ void d_for_impl(F&& f, std::integer_sequence<int, I...>) { (f(std::integral_constant<int, I>{}), ...); }
@@ -75,6 +87,6 @@ __device__ __forceinline__ void d_sload_start(int& r, const int32_t* base, int o
 }
 __device__ __forceinline__ void d_sload_land(int& r) { asm volatile("s_waitcnt lgkmcnt(0)" : "+s"(r) :: "memory"); }
 
-int launch_prefill_d256_fp8(const mi355_attn_params& p, hipStream_t stream);   // prefill_d256_fp8.hip: an fp8 cache
+int launch_prefill_d256_fp8(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks);   // prefill_d256_fp8.hip: an fp8 cache
 
 }  // namespace mi355

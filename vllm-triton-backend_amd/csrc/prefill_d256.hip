@@ -34,6 +34,13 @@
 // (P <= 2^8: exact in f32 sums, far inside bf16 / f16; rescaling O is 128 trips through the accumulator registers).
 // No fixed reference, so f16 needs no range check and no fix-up launch. Only tiles on the diagonal, the sequence's last
 // partial tile and (SW) the window's edge tiles are masked.
+//
+// Key-split form (KS, library 0.13.0; grid.y = splits): workgroup (x, s) walks the s-th even share of its Q block's own tile
+// range - from the window's first tile with SW - and writes normalised partial rows (query type) and their lse (f32) to the
+// workspace buffers of split s; merge_key_splits_kernel (prefill_mfma.hip) folds them and adds the sink, once. Nothing else
+// changes: the prefetch starts at the share's first tile, stage parity counts from it, masks and the tail clamp are functions
+// of absolute key positions; a share without a tile, or without a visible key for a row, leaves that row at out 0 / lse -inf.
+// The one-pass instantiations (KS = false) keep their code.
 #include <cstdlib>
 
 #include "prefill_d256.h"
@@ -46,7 +53,7 @@ constexpr int kDStageB = 2 * kDTileB;       // K tile then V tile
 constexpr int kDLds = 2 * kDStageB;         // two stages
 static_assert(4 * 32 * kDORS <= kDLds && kDLds <= 160 * 1024, "prefill_d256_kernel: LDS map");
 
-template <typename T, bool SW>
+template <typename T, bool SW, bool KS>
 __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) {
   using ops = d256_ops<T>;
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -95,8 +102,12 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) 
   const int wave_keys = min(ctx_len + w_tok_hi + 1, seq_len);
   const bool wave_has_rows = w_tok_lo <= w_tok_hi;
   const int wave_first_key = SW ? ctx_len + w_tok_lo - sw + 1 : 0;       // no row of the wave sees a key below
-  const int tile_lo = SW ? max(0, ctx_len + tok0 - sw + 1) / kDTile : 0;
-  const int tile_hi = (n_keys_wg + kDTile - 1) / kDTile;
+  int tile_lo = SW ? max(0, ctx_len + tok0 - sw + 1) / kDTile : 0;
+  int tile_hi = (n_keys_wg + kDTile - 1) / kDTile;
+  // key-split launch: this workgroup's share of those tiles - possibly none, it then writes 0 / -inf, which the merge weighs
+  // with 0. Masks and the tail clamp are functions of absolute key positions, the pipeline's parity of tile - tile_lo.
+  const int ksplit = KS ? (int)blockIdx.y : 0;
+  if constexpr (KS) d_key_share(tile_lo, tile_hi, ksplit, a.key_splits);
 
   // ---- Q' = Q * scale * log2(e) into a[128 ..]: lane (r16, g4) holds Q'[row][32 ks + 8 g4 .. + 7] --------------
   const float scale2 = p.scale * kDLog2e;
@@ -317,8 +328,9 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) 
     l += lane_xor32(l);
     // attention sink: the row's (m, l) is final here
     const float sink_w = (p.sinks && row_ok[rb]) ? fold_sink<true>(m, l, p.sinks[hq[rb]]) : 1.0f;
-    if (p.lse && row_ok[rb] && g4 == 0)
-      p.lse[(int64_t)(q_start + tok_local[rb]) * p.lse_stride_token + hq[rb]] = l > 0.0f ? (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f : -INFINITY;
+    float* const lse_base = KS ? p.lse + (int64_t)ksplit * a.lse_split_stride : p.lse;
+    if (lse_base && row_ok[rb] && g4 == 0)
+      lse_base[(int64_t)(q_start + tok_local[rb]) * p.lse_stride_token + hq[rb]] = l > 0.0f ? (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f : -INFINITY;
     inv[rb] = (row_ok[rb] && l > 0.0f) ? sink_w / l : 0.0f;
   }
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");   // the last P.V results are in their registers
@@ -336,6 +348,7 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) 
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int orow = lane >> 5, och = lane & 31;
+  uint16_t* const out_base = KS ? (uint16_t*)p.out + (int64_t)ksplit * a.out_split_stride : (uint16_t*)p.out;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int r = 2 * j + orow;
@@ -343,7 +356,7 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_kernel(const D256Args a) 
     const int tok = tok0 + m / G;
     const du32x4_t v = *(const du32x4_t*)(ost + r * kDORS + och * 16);
     if (m < BQ * G && tok < q_len)
-      __builtin_nontemporal_store(v, (du32x4_t*)((uint16_t*)p.out + (int64_t)(q_start + tok) * p.out_stride_token +
+      __builtin_nontemporal_store(v, (du32x4_t*)(out_base + (int64_t)(q_start + tok) * p.out_stride_token +
                                                  (int64_t)(head * G + m % G) * p.out_stride_head + och * 8));
   }
 }
@@ -367,8 +380,8 @@ bool prefill_d256_applicable(const mi355_attn_params& p) {
   return true;
 }
 
-template <typename T, bool SW>
-static int launch_d256_t(const mi355_attn_params& p, hipStream_t stream) {
+template <typename T, bool SW, bool KS>
+static int launch_d256_t(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
   D256Args a;
   a.p = p;
   a.group = p.num_q_heads / p.num_kv_heads;
@@ -376,25 +389,34 @@ static int launch_d256_t(const mi355_attn_params& p, hipStream_t stream) {
   a.page_shift = __builtin_ctz((unsigned)p.page_size);
   a.k_page_b = (uint32_t)(p.k_stride_page * 2); a.k_slot_b = (uint32_t)(p.k_stride_slot * 2);
   a.v_page_b = (uint32_t)(p.v_stride_page * 2); a.v_slot_b = (uint32_t)(p.v_stride_slot * 2);
+  a.key_splits = KS ? ks->splits : 1;
+  a.out_split_stride = KS ? ks->out_split_stride : 0;
+  a.lse_split_stride = KS ? ks->lse_split_stride : 0;
   const int qblocks = p.num_tokens / a.block_q + p.num_seqs;   // static upper bound, as for the other Q-block kernels
   static std::atomic<uint64_t> lds_opt_in{0};
-  const int rc0 = ensure_dynamic_lds((const void*)prefill_d256_kernel<T, SW>, kDLds, lds_opt_in, "hipFuncSetAttribute(prefill_d256)");
+  const int rc0 = ensure_dynamic_lds((const void*)prefill_d256_kernel<T, SW, KS>, kDLds, lds_opt_in, "hipFuncSetAttribute(prefill_d256)");
   if (rc0 != MI355_OK) return rc0;
-  hipLaunchKernelGGL((prefill_d256_kernel<T, SW>), dim3(qblocks * p.num_kv_heads), dim3(256), kDLds, stream, a);
+  hipLaunchKernelGGL((prefill_d256_kernel<T, SW, KS>), dim3(qblocks * p.num_kv_heads, a.key_splits), dim3(256), kDLds, stream, a);
   const int rc = check_hip(hipGetLastError(), "prefill_d256_kernel launch");
   if (rc == MI355_OK) set_kernel_name(SW ? "prefill_mfma_d256_sw" : "prefill_mfma_d256");
   return rc;
 }
 
-int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream) {
-  if (!prefill_supported(p) || !prefill_d256_applicable(p)) {
+template <typename T>
+static int launch_d256_sw(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
+  if (ks) return p.sliding_window > 0 ? launch_d256_t<T, true, true>(p, stream, ks) : launch_d256_t<T, false, true>(p, stream, ks);
+  return p.sliding_window > 0 ? launch_d256_t<T, true, false>(p, stream, ks) : launch_d256_t<T, false, false>(p, stream, ks);
+}
+
+// ks: the key-split launch (launch_prefill_ws: p.out / p.lse are the workspace's partial buffers and never null, p.sinks is
+// null - the merge behind this launch folds the sink in, once - and the name gets its _ksplit suffix there)
+int launch_prefill_d256(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
+  if (!prefill_supported(p) || !prefill_d256_applicable(p) || (ks && (ks->splits < 2 || !p.lse || p.sinks))) {
     set_error("prefill_d256_kernel does not support this configuration");
     return MI355_ERR_UNSUPPORTED;
   }
-  if (p.kv_dtype != p.q_dtype) return launch_prefill_d256_fp8(p, stream);
-  const bool bf = p.q_dtype == MI355_BF16;
-  if (p.sliding_window > 0) return bf ? launch_d256_t<bf16_t, true>(p, stream) : launch_d256_t<f16_t, true>(p, stream);
-  return bf ? launch_d256_t<bf16_t, false>(p, stream) : launch_d256_t<f16_t, false>(p, stream);
+  if (p.kv_dtype != p.q_dtype) return launch_prefill_d256_fp8(p, stream, ks);
+  return p.q_dtype == MI355_BF16 ? launch_d256_sw<bf16_t>(p, stream, ks) : launch_d256_sw<f16_t>(p, stream, ks);
 }
 
 }  // namespace mi355

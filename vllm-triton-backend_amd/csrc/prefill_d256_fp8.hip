@@ -32,6 +32,9 @@
 //
 // Nothing outside the sequence reaches a sum: rows past it re-read its last row (valid fp8 data, never a stale 0x7f byte), and
 // a masked score is -inf, whose P is exactly 0.
+//
+// Key-split form (KS, library 0.13.0): as prefill_d256_kernel's - grid.y = splits, an even share of the Q block's own tile
+// range, partial rows (v_scale applied) and lse to the workspace buffers of split s.
 #include <cstdlib>
 
 #include "prefill_d256.h"
@@ -62,7 +65,7 @@ MI355_DEF_D256_WIDEN(f16_t, e4m3_t, "v_cvt_scalef32_pk_f16_fp8")
 MI355_DEF_D256_WIDEN(f16_t, e5m2_t, "v_cvt_scalef32_pk_f16_bf8")
 #undef MI355_DEF_D256_WIDEN
 
-template <typename T, typename KVT, bool SW>
+template <typename T, typename KVT, bool SW, bool KS>
 __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args a) {
   using ops = d256_ops<T>;
   using wid = d256_widen<T, KVT>;
@@ -112,8 +115,12 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args
   const int wave_keys = min(ctx_len + w_tok_hi + 1, seq_len);
   const bool wave_has_rows = w_tok_lo <= w_tok_hi;
   const int wave_first_key = SW ? ctx_len + w_tok_lo - sw + 1 : 0;       // no row of the wave sees a key below
-  const int tile_lo = SW ? max(0, ctx_len + tok0 - sw + 1) / kDTile : 0;
-  const int tile_hi = (n_keys_wg + kDTile - 1) / kDTile;
+  int tile_lo = SW ? max(0, ctx_len + tok0 - sw + 1) / kDTile : 0;
+  int tile_hi = (n_keys_wg + kDTile - 1) / kDTile;
+  // key-split launch: this workgroup's share of those tiles - possibly none, it then writes 0 / -inf, which the merge weighs
+  // with 0. Masks and the tail clamp are functions of absolute key positions, the pipeline's parity of tile - tile_lo.
+  const int ksplit = KS ? (int)blockIdx.y : 0;
+  if constexpr (KS) d_key_share(tile_lo, tile_hi, ksplit, a.key_splits);
 
   // ---- Q' = Q * scale * log2(e) * k_scale into a[128 ..]: lane (r16, g4) holds, for k-step ks, the head dims
   //      64 (ks >> 1) + 16 g4 + 8 (ks & 1) .. + 7 - the order in which a 16-byte fp8 read of K delivers two k-steps ----
@@ -345,8 +352,9 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args
     l += lane_xor32(l);
     // attention sink: the row's (m, l) is final here
     const float sink_w = (p.sinks && row_ok[rb]) ? fold_sink<true>(m, l, p.sinks[hq[rb]]) : 1.0f;
-    if (p.lse && row_ok[rb] && g4 == 0)
-      p.lse[(int64_t)(q_start + tok_local[rb]) * p.lse_stride_token + hq[rb]] = l > 0.0f ? (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f : -INFINITY;
+    float* const lse_base = KS ? p.lse + (int64_t)ksplit * a.lse_split_stride : p.lse;
+    if (lse_base && row_ok[rb] && g4 == 0)
+      lse_base[(int64_t)(q_start + tok_local[rb]) * p.lse_stride_token + hq[rb]] = l > 0.0f ? (m + __builtin_amdgcn_logf(l)) * 0.6931471805599453f : -INFINITY;
     inv[rb] = (row_ok[rb] && l > 0.0f) ? v_sc * sink_w / l : 0.0f;      // (V was summed unscaled)
   }
   asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 3" ::: "memory");   // the last P.V results are in their registers
@@ -364,6 +372,7 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args
   __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
   __builtin_amdgcn_wave_barrier();
   const int orow = lane >> 5, och = lane & 31;
+  uint16_t* const out_base = KS ? (uint16_t*)p.out + (int64_t)ksplit * a.out_split_stride : (uint16_t*)p.out;
 #pragma unroll
   for (int j = 0; j < 16; ++j) {
     const int r = 2 * j + orow;
@@ -371,7 +380,7 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args
     const int tok = tok0 + m / G;
     const du32x4_t v = *(const du32x4_t*)(ost + r * kDORS + och * 16);
     if (m < BQ * G && tok < q_len)
-      __builtin_nontemporal_store(v, (du32x4_t*)((uint16_t*)p.out + (int64_t)(q_start + tok) * p.out_stride_token +
+      __builtin_nontemporal_store(v, (du32x4_t*)(out_base + (int64_t)(q_start + tok) * p.out_stride_token +
                                                  (int64_t)(head * G + m % G) * p.out_stride_head + och * 8));
   }
 }
@@ -379,8 +388,8 @@ __global__ __launch_bounds__(256, 1) void prefill_d256_fp8_kernel(const D256Args
 // ---------------------------------------------------------------------------------------------
 // host side (the conditions: prefill_d256_applicable(), prefill_d256.hip)
 // ---------------------------------------------------------------------------------------------
-template <typename T, typename KVT, bool SW>
-static int launch_d256_fp8_t(const mi355_attn_params& p, hipStream_t stream) {
+template <typename T, typename KVT, bool SW, bool KS>
+static int launch_d256_fp8_t(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
   D256Args a;
   a.p = p;
   a.group = p.num_q_heads / p.num_kv_heads;
@@ -388,30 +397,34 @@ static int launch_d256_fp8_t(const mi355_attn_params& p, hipStream_t stream) {
   a.page_shift = __builtin_ctz((unsigned)p.page_size);
   a.k_page_b = (uint32_t)p.k_stride_page; a.k_slot_b = (uint32_t)p.k_stride_slot;      // one byte an element
   a.v_page_b = (uint32_t)p.v_stride_page; a.v_slot_b = (uint32_t)p.v_stride_slot;
+  a.key_splits = KS ? ks->splits : 1;
+  a.out_split_stride = KS ? ks->out_split_stride : 0;
+  a.lse_split_stride = KS ? ks->lse_split_stride : 0;
   const int qblocks = p.num_tokens / a.block_q + p.num_seqs;   // static upper bound, as for the other Q-block kernels
   static std::atomic<uint64_t> lds_opt_in{0};
-  const int rc0 = ensure_dynamic_lds((const void*)prefill_d256_fp8_kernel<T, KVT, SW>, kFLds, lds_opt_in, "hipFuncSetAttribute(prefill_d256_fp8)");
+  const int rc0 = ensure_dynamic_lds((const void*)prefill_d256_fp8_kernel<T, KVT, SW, KS>, kFLds, lds_opt_in, "hipFuncSetAttribute(prefill_d256_fp8)");
   if (rc0 != MI355_OK) return rc0;
-  hipLaunchKernelGGL((prefill_d256_fp8_kernel<T, KVT, SW>), dim3(qblocks * p.num_kv_heads), dim3(256), kFLds, stream, a);
+  hipLaunchKernelGGL((prefill_d256_fp8_kernel<T, KVT, SW, KS>), dim3(qblocks * p.num_kv_heads, a.key_splits), dim3(256), kFLds, stream, a);
   const int rc = check_hip(hipGetLastError(), "prefill_d256_fp8_kernel launch");
   if (rc == MI355_OK) set_kernel_name(SW ? "prefill_mfma_fp8_d256_sw" : "prefill_mfma_fp8_d256");
   return rc;
 }
 
 template <typename T, typename KVT>
-static int launch_d256_fp8_sw(const mi355_attn_params& p, hipStream_t stream) {
-  return p.sliding_window > 0 ? launch_d256_fp8_t<T, KVT, true>(p, stream) : launch_d256_fp8_t<T, KVT, false>(p, stream);
+static int launch_d256_fp8_sw(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
+  if (ks) return p.sliding_window > 0 ? launch_d256_fp8_t<T, KVT, true, true>(p, stream, ks) : launch_d256_fp8_t<T, KVT, false, true>(p, stream, ks);
+  return p.sliding_window > 0 ? launch_d256_fp8_t<T, KVT, true, false>(p, stream, ks) : launch_d256_fp8_t<T, KVT, false, false>(p, stream, ks);
 }
 
-int launch_prefill_d256_fp8(const mi355_attn_params& p, hipStream_t stream) {
+int launch_prefill_d256_fp8(const mi355_attn_params& p, hipStream_t stream, const KeySplitCtx* ks) {
   const bool fp8 = p.kv_dtype == MI355_FP8_E4M3 || p.kv_dtype == MI355_FP8_E5M2;
-  if (!fp8 || !prefill_supported(p) || !prefill_d256_applicable(p)) {
+  if (!fp8 || !prefill_supported(p) || !prefill_d256_applicable(p) || (ks && (ks->splits < 2 || !p.lse || p.sinks))) {
     set_error("prefill_d256_fp8_kernel does not support this configuration");
     return MI355_ERR_UNSUPPORTED;
   }
   const bool bf = p.q_dtype == MI355_BF16;
-  if (p.kv_dtype == MI355_FP8_E4M3) return bf ? launch_d256_fp8_sw<bf16_t, e4m3_t>(p, stream) : launch_d256_fp8_sw<f16_t, e4m3_t>(p, stream);
-  return bf ? launch_d256_fp8_sw<bf16_t, e5m2_t>(p, stream) : launch_d256_fp8_sw<f16_t, e5m2_t>(p, stream);
+  if (p.kv_dtype == MI355_FP8_E4M3) return bf ? launch_d256_fp8_sw<bf16_t, e4m3_t>(p, stream, ks) : launch_d256_fp8_sw<f16_t, e4m3_t>(p, stream, ks);
+  return bf ? launch_d256_fp8_sw<bf16_t, e5m2_t>(p, stream, ks) : launch_d256_fp8_sw<f16_t, e5m2_t>(p, stream, ks);
 }
 
 }  // namespace mi355

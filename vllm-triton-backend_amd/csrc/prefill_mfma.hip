@@ -1622,7 +1622,8 @@ bool prefill_runs_without_key_splits(const mi355_attn_params& p) { return plan_k
 // this kernel is ahead at every one (Hq 16 / Hk 8, bf16, graph replay, us per launch, register-staged | this, the former
 // twice within 0.3 %: 1 x 512 28.5 | 25.0, 1 x 1024 47.8 | 41.6, 1 x 2048 without key splits 90.3 | 78.2, 1 x 4096 188.6 | 163.8,
 // 16 x 4096 3158 | 2768, 1 x 16384 2651 | 2331; window 1024: 1 x 4096 112.0 | 93.4, 16 x 4096 1641 | 1344, 1 x 16384 451 | 375;
-// profiles/r08/). Where plan_key_splits() splits (1 x 2048: 76.1 us on two splits) the call stays on the key-split launch.
+// profiles/r08/). Where plan_key_splits() splits (1 x 2048: 76.1 us on two splits) the call stays on the key-split launch -
+// which, since library 0.13.0, runs on this kernel's key-split form (below).
 constexpr int kD256MinKeys = 512;
 // The same rule for an fp8 cache (prefill_d256_fp8_kernel, prefill_d256_fp8.hip; library 0.10.0), with a minimum of its own:
 // again the smallest length measured, and that kernel is ahead at every one (Hq 16 / Hk 8, bf16 over e4m3, graph replay, us per
@@ -1630,9 +1631,20 @@ constexpr int kD256MinKeys = 512;
 // splits 80.3 | 75.7, 1 x 4096 171.0 | 161.0, 16 x 4096 2722 | 2544, 1 x 16384 2404 | 2287; window 1024: 1 x 4096 104.3 | 89.5,
 // 16 x 4096 1528 | 1283, 1 x 16384 413.1 | 353.4; profiles/r09/).
 constexpr int kD256Fp8MinKeys = 512;
-bool prefill_d256_selected(const mi355_attn_params& p) {
+// Library 0.13.0: a key-split launch (ks) of such a call goes to the same kernels' key-split form under the same conditions -
+// grid.y = splits, partial rows and lse to the workspace, merge_key_splits_kernel behind it. plan_key_splits() is unchanged
+// (so is the workspace); at its plan the form is ahead of the register-staged kernel's key-split launch in every cell measured
+// (Hq 16 / Hk 8, one sequence, graph replay, us per call with the merge, register-staged twice | this twice; profiles/r12/):
+// bf16 cache  512-token chunk at 8k / 32k keys 109.9 109.9 | 98.0 97.9, 377.7 378.1 | 341.4 340.4; 2048-token chunk 322.5 322.5 |
+//             284.4 284.3, 1397.6 1397.2 | 1267.4 1265.7; 1 x 2048 76.6 76.7 | 68.7 68.5
+// e4m3 cache  101.7 101.9 | 94.3 94.4, 320.1 320.4 | 298.1 297.3; 292.1 293.4 | 272.3 270.2, 1164.3 1166.1 | 1088.2 1085.3; 71.9 72.2 | 67.5 67.2
+// window 1024 44.7 44.6 | 40.4 40.4, 44.8 44.9 | 40.7 40.8; 80.7 81.1 | 70.0 70.0, 80.4 80.4 | 70.0 69.9; 77.6 77.5 | 67.0 66.7
+// The sweep of the split count says a plan of its own would gain more (512-token chunks: 4 splits 87.0 us where the plan's 8
+// take 97.9; window 1024 and a 2048-token chunk: one pass 48.6 where the plan's 2 take 70.0) - not adopted here, see r12.
+bool prefill_d256_selected(const mi355_attn_params& p, const KeySplitCtx* ks) {
   static const char* const variant = lab_env("MI355_PREFILL");
-  if (variant || !prefill_supported(p) || !prefill_d256_applicable(p) || plan_key_splits(p).splits > 1) return false;
+  if (variant || !prefill_supported(p) || !prefill_d256_applicable(p)) return false;
+  if (ks ? (ks->splits < 2 || ks->wide || !p.lse || p.sinks) : plan_key_splits(p).splits > 1) return false;
   return p.kernel_select == MI355_SELECT_2D || p.max_seqlen_k >= (p.kv_dtype == p.q_dtype ? kD256MinKeys : kD256Fp8MinKeys);
 }
 
@@ -1687,7 +1699,7 @@ int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySpli
   // want the wider ones). MI355_PREFILL=lat pins it wherever it applies.
   if (!ks && prefill_lat_selected(p)) return launch_prefill_lat(p, stream);
   if (p.write_new_kv && (ks || !prefill_dma_selected(p))) { set_error("write_new_kv: this prefill step is not served with a fused cache write (mi355_decode_write_fusable)"); return MI355_ERR_UNSUPPORTED; }
-  if (!ks && prefill_d256_selected(p)) return launch_prefill_d256(p, stream);
+  if (prefill_d256_selected(p, ks)) return launch_prefill_d256(p, stream, ks);
   if (!feat && p.head_size == 128 && !v1 && p.kv_dtype == p.q_dtype) {
     // 8 waves / 256-row Q blocks / 3 stages when that still gives every CU two workgroups' worth of Q blocks
     // (it holds one at a time) and the sequences are long enough to amortise a workgroup's un-overlapped
@@ -1712,7 +1724,8 @@ int launch_prefill(const mi355_attn_params& p, hipStream_t stream, const KeySpli
   // measured 112 TFLOP/s against the register-staged kernel's 494: without staging registers hipcc still moves several
   // hundred values per tile between VGPRs and accumulator registers (432 v_accvgpr_read + 225 v_accvgpr_write per tile
   // in the ISA, 750 bytes of scratch). Head size 256 needs the hand-owned register file of prefill_pw_kernel:
-  // prefill_d256_kernel, prefill_d256.hip, taken above; what reaches the cases below at that size is fp8, features, key splits.)
+  // prefill_d256_kernel, prefill_d256.hip, taken above with or without key splits; what reaches the cases below at that size is
+  // soft-cap / ALiBi, other head sizes run at 256, MI355_PREFILL=v1.)
 #define MI355_PREFILL_CASE(KV, DD)                                                                        \
   case DD:                                                                                                \
     if (feat) return bf ? launch_prefill_t<bf16_t, KV<bf16_t>, DD, true>(p, stream, ks) : launch_prefill_t<f16_t, KV<f16_t>, DD, true>(p, stream, ks); \
